@@ -306,6 +306,50 @@ def sp_union(a, m):
     return u
 
 
+DUMP_SAMPLE = 1 << 20  # entries kept of each N x M output by --dump-outputs
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_sample_index(N, M):
+    """Which entries of an N x M output --dump-outputs writes: flat row-major indices
+    t * M + x, sorted.  All of them when there are at most DUMP_SAMPLE, otherwise a
+    sample drawn with a fixed seed, so the same N and M always give the same entries."""
+    if N * M <= DUMP_SAMPLE:
+        return np.arange(N * M, dtype=np.int64)
+    return np.unique(np.random.RandomState(20240607).randint(0, N * M, size=DUMP_SAMPLE,
+                                                             dtype=np.int64))
+
+
+def gather_sample(comm, dd, vec, idx):
+    """The entries `idx` (dump_sample_index) of the distributed vector `vec`, read on the
+    device by the rank whose time slab holds them and assembled on rank 0 (None on the
+    other ranks).  Collective: every rank calls it."""
+    import torch
+    t, xs = idx // dd.M, idx % dd.M
+    mine = (t >= dd.t_begin) & (t < dd.t_end)
+    dev = vec.buf.device
+    vals = vec.buf[torch.from_numpy(xs[mine]).to(dev),
+                   torch.from_numpy(t[mine] - dd.t_begin).to(dev)].cpu().numpy()
+    parts = comm.gather(vals)
+    if parts is None:
+        return None
+    out = np.empty(len(idx), dtype=np.float64)
+    for (b, e), part in zip(dd.dof_distribution, parts):
+        out[(t >= b) & (t < e)] = part
+    return out
+
+
+def write_dumps(path, arrays):
+    """--dump-outputs: one float64 .npy per output, DUMP_MAX_BYTES at most in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+    print('bench.py: wrote %d outputs (%.1f MB) to %s' % (len(arrays), total / 2**20, path),
+          file=sys.stderr)
+
+
 def profiler_preloaded():
     """True under rocprofv3 / rocprof: their preloaded tool library initialises
     the GPU before the program starts (it does with --pmc)."""
@@ -359,7 +403,14 @@ def main():
                     help='seconds of untimed applies before the warm-up steps')
     ap.add_argument('--cpu-baseline-only', action='store_true',
                     help='(internal) run the CPU baseline alone and print its record as JSON')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the timed applies and solves '
+                         'computed last to DIR/<name>.npy (float64; a fixed, seeded sample '
+                         'of each N x M vector): kron_y, and pcg_<arithmetic>_w and '
+                         'pcg_<arithmetic>_r_dot_Pr for every timed solve')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         # started as plain `python bench.py --gpus N` (the reference's protocol is
@@ -484,6 +535,10 @@ def main():
     comm.Barrier()
     dt = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1) / args.steps
+    dumps = {}
+    if args.dump_outputs:
+        sample = dump_sample_index(N, M)
+        dumps['kron_y'] = gather_sample(comm, dd, y, sample)  # y of the last timed step
 
     # kernels alone (several ranks): the same applies with the halo already
     # present, so that the roofline figure of the kernel excludes the exchange
@@ -540,9 +595,12 @@ def main():
             torch.cuda.synchronize()
             stamps.append(time.perf_counter())
 
-        _, its = PCG(h.WT_S_W, h.P, h.rhs, kmax=args.solve_iters + 2,
+        w, its = PCG(h.WT_S_W, h.P, h.rhs, kmax=args.solve_iters + 2,
                      history=hist, callback=cb)
         comm.Barrier()
+        if args.dump_outputs:
+            dumps['pcg_%s_w' % arithmetic] = gather_sample(comm, h.dofs_distr, w, sample)
+            dumps['pcg_%s_r_dot_Pr' % arithmetic] = np.asarray(hist, dtype=np.float64)
         # stamps[k] is taken inside iteration k+1, after its operator apply:
         # consecutive stamps are exactly one PCG iteration apart
         n_it = len(stamps) - 1
@@ -613,6 +671,8 @@ def main():
 
     if rank != 0:
         return
+    if args.dump_outputs:
+        write_dumps(args.dump_outputs, dumps)
     if args.gpus == 1 and size == 1 and not args.no_cpu_baseline:
         torch.cuda.synchronize()
         cpu = run_cpu_baseline()

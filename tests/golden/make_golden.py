@@ -173,6 +173,41 @@ class Hierarchy:
         self.R_mats = [P.T.tocsr() for P in P_mats]
 
 
+# the problems of the g3_* fixtures: name, mesh constructor, J_space, J_time
+G3_PROBLEMS = [
+    ('square', 'construct_2d_square_mesh', 2, 3),
+    ('lshape', 'construct_2d_lshape_mesh', 1, 3),
+    ('square3', 'construct_2d_square_mesh', 3, 2),
+    ('cube', 'construct_3d_cube_mesh', 1, 2),
+]
+
+
+def g3_build_side(mesh_mod, asm, meshfn, J_space, J_time):
+    """The part of a g3_* fixture that comes from this build, not from the
+    reference: the matrices and load vectors of our own mesh and assembly, and
+    the seeded input X.  Returns the fixture's entries for them, the matrices,
+    and the generator that drew X (its next draw is the multigrid right-hand
+    side)."""
+    mesh, _ = getattr(mesh_mod, meshfn)(J_space)
+    tmesh = mesh_mod.construct_interval(2**J_time)
+    A_t, L_t, M_t, G_t, u0_t = asm.time_matrices(tmesh)
+    M_x, A_x = asm.space_matrices(mesh, scipy_path=True)  # the generator does not load libstk
+    P_mats = asm.prolongation_matrices(mesh)
+    u0_x = asm.space_load(
+        mesh, lambda *c: np.prod([np.sin(np.pi * ck) for ck in c], axis=0), numpy_path=True)
+    N, M = A_t.shape[0], M_x.shape[0]
+    rng = np.random.RandomState(128)
+    X = rng.rand(N, M)
+    out = {'N': N, 'M': M, 'J_time': J_time, 'J_space': J_space, 'X': X,
+           'u0_t': u0_t, 'u0_x': u0_x, 'nP': len(P_mats)}
+    for nm, m in [('A_t', A_t), ('L_t', L_t), ('M_t', M_t), ('G_t', G_t),
+                  ('M_x', M_x), ('A_x', A_x)]:
+        out.update(csr_parts(nm, m))
+    for j, P in enumerate(P_mats):
+        out.update(csr_parts('P%d' % j, P))
+    return out, (A_t, L_t, M_t, G_t, u0_t, M_x, A_x, P_mats, u0_x, X), rng
+
+
 def main():
     install_standins()
     sys.path.insert(0, REF)
@@ -245,32 +280,13 @@ def main():
         v.X_loc[:] = X
         return v
 
-    for pname, meshfn, J_space, J_time in [
-        ('square', mesh_mod.construct_2d_square_mesh, 2, 3),
-        ('lshape', mesh_mod.construct_2d_lshape_mesh, 1, 3),
-        ('square3', mesh_mod.construct_2d_square_mesh, 3, 2),
-        ('cube', mesh_mod.construct_3d_cube_mesh, 1, 2),
-    ]:
+    for pname, meshfn, J_space, J_time in G3_PROBLEMS:
         if only and 'g3_' + pname not in only:
             continue
-        mesh, _ = meshfn(J_space)
-        tmesh = mesh_mod.construct_interval(2**J_time)
-        A_t, L_t, M_t, G_t, u0_t = asm.time_matrices(tmesh)
-        M_x, A_x = asm.space_matrices(mesh, scipy_path=True)  # the generator does not load libstk
-        P_mats = asm.prolongation_matrices(mesh)
-        u0_x = asm.space_load(
-            mesh, lambda *c: np.prod([np.sin(np.pi * ck) for ck in c], axis=0), numpy_path=True)
+        out, mats, rng = g3_build_side(mesh_mod, asm, meshfn, J_space, J_time)
+        A_t, L_t, M_t, G_t, u0_t, M_x, A_x, P_mats, u0_x, X = mats
         N, M = A_t.shape[0], M_x.shape[0]
         dd = DofDistributionMPI(comm, N, M)
-        rng = np.random.RandomState(128)
-        X = rng.rand(N, M)
-        out = {'N': N, 'M': M, 'J_time': J_time, 'J_space': J_space, 'X': X,
-               'u0_t': u0_t, 'u0_x': u0_x, 'nP': len(P_mats)}
-        for nm, m in [('A_t', A_t), ('L_t', L_t), ('M_t', M_t), ('G_t', G_t),
-                      ('M_x', M_x), ('A_x', A_x)]:
-            out.update(csr_parts(nm, m))
-        for j, P in enumerate(P_mats):
-            out.update(csr_parts('P%d' % j, P))
 
         x = vec_from(dd, X)
         # G3: Kronecker applies

@@ -7,6 +7,7 @@ import sys
 
 import numpy as np
 import torch
+import torch.distributed as torch_dist
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -14,8 +15,20 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'spacetime-fullgrid-parallel_amd'))
 
 from oracle import partition, wavelets  # noqa: E402
-from source.comm import MPI  # noqa: E402
+from source.comm import MPI, Comm  # noqa: E402
 from source.mpi_vector import DofDistributionMPI, KronVectorMPI  # noqa: E402
+
+
+def _host_barrier(self):
+    """Comm.Barrier for this host-only job.  torch.distributed.barrier() probes for an
+    accelerator whatever the backend, and on a machine with a GPU that starts the GPU
+    runtime in every rank: eight ranks would hold the GPU open at once.  A gloo
+    all-reduce synchronises the ranks the same way without touching it."""
+    if self.collective:
+        torch_dist.all_reduce(torch.zeros(1), group=self.group)
+
+
+Comm.Barrier = _host_barrier
 
 
 def main():
@@ -148,6 +161,10 @@ def main():
     comm.Barrier()
     if rank == 0:
         print('mp_comm_worker ok, size', size)
+    # shut gloo down while the interpreter is alive: its worker threads release the
+    # tensors of finished work, which takes the GIL, and a thread that asks for the GIL
+    # during interpreter shutdown is ended there (std::terminate, SIGABRT)
+    torch_dist.destroy_process_group()
 
 
 if __name__ == '__main__':

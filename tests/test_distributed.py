@@ -37,8 +37,12 @@ def _run(worker, nproc, extra_env=None, timeout=600):
 
 @pytest.mark.parametrize('nproc', [2, 3, 5, 8])
 def test_comm_layer_gloo_cpu(nproc):
+    # no process of this test may open the GPU, or on a machine with one the ranks
+    # would hold it open all at once: torch decides availability from the (empty)
+    # list of visible devices instead of starting the HIP runtime to count them
     out = _run('mp_comm_worker.py', nproc, {'HIP_VISIBLE_DEVICES': '',
-                                            'CUDA_VISIBLE_DEVICES': ''})
+                                            'CUDA_VISIBLE_DEVICES': '',
+                                            'PYTORCH_NVML_BASED_CUDA_CHECK': '1'})
     assert 'mp_comm_worker ok' in out
 
 

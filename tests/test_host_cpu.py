@@ -184,6 +184,9 @@ def test_gauss_seidel_schedule_deep_chain():
 @pytest.fixture
 def host_uploads(monkeypatch):
     from source import _lib
+    # the builders' host path on every machine: where a GPU is present they would
+    # otherwise build on the device, handing these host tensors to a kernel
+    monkeypatch.setattr(_lib, 'compute_device', lambda: torch.device('cpu'))
     monkeypatch.setattr(_lib, 'to_dev', lambda a, dtype=None: torch.from_numpy(
         np.ascontiguousarray(a)))
     monkeypatch.setattr(_lib, 'ptr', lambda t: None if t is None else
