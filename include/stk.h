@@ -43,8 +43,58 @@ const char *stk_last_error(void);
 int stk_version(void);
 /* Device properties the host side sizes launches with (CUs, wavefront). */
 int stk_device_info(int32_t *n_cu, int32_t *wave_size, int64_t *hbm_bytes);
-/* Launch-geometry knobs for benchmarking sweeps ("kron_block": 0 = automatic,
- * or 256 / 512 / 1024 threads per workgroup).  Results never depend on them. */
+/* Process-wide tuning keys, settable from any thread.  Returns non-zero, with
+ * stk_last_error naming the key, for an unknown key or a value outside the key's
+ * range.  Launch keys act on the next launch; plan keys are read when a plan is
+ * created and hold for its lifetime.  "Bit-identical" means results never depend
+ * on the key; "rounding" means the last bits may change.
+ *   kron_block           (launch, 0..1024, default 0) threads per workgroup of
+ *                        stk_kron_sum_apply: 256, 512 or 1024; any other value
+ *                        chooses by lane use.  Bit-identical.
+ *   ell_wg_per_cu        (launch, 0..16, default 0) persistent workgroups per CU
+ *                        of stk_kron_ell_apply; 0 = 2 for K >= 12, else 3.
+ *                        Bit-identical.
+ *   ell_force_wide       (launch, 0..1, default 0) 64-bit addressing in the
+ *                        sliced-ELL Kronecker kernels on small slabs (tests).
+ *                        Bit-identical.
+ *   rows_force_wide      (launch, 0..1, default 0) the same for the ELL row engine
+ *                        (stk_mg_*, stk_ell_rows_*).  Bit-identical.
+ *   pack_rows            (plan, 1..2, default 2) matrix rows per slot row of the
+ *                        packed form of stk_kron_plan_create.  Bit-identical.
+ *   pack_multi_lanes     (launch, 0..2, default 1) stk_kron_pack_apply_multi:
+ *                        1 = a lane group per term on long slabs, turns on short
+ *                        ones; 2 = lane groups always; 0 = turns always.
+ *                        Bit-identical.
+ *   pack_check_steps     (launch, 0..1, default 0) stk_kron_pack_apply_multi_steps
+ *                        checks the stated time steps against the factors (one
+ *                        stream synchronisation per call; tests).  No effect on
+ *                        results that pass the check.
+ *   mg_strip_mb          (launch, 0..1048576, default 250) working set in MB of a
+ *                        strip of the strip-wise Gauss-Seidel sweeps; 0 = off.
+ *                        Bit-identical.
+ *   mg_strip_width       (launch, 0..1024, default 2) least strip width in units
+ *                        of (sweeps x groups) bands; 0 = as thin as possible
+ *                        (tests).  Bit-identical.
+ *   mg_strips_used       (counter) launches that came from a strip table: 0
+ *                        resets it, n > 0 fails unless at least n happened.
+ *   mg_zero_start        (launch, 0..1, default 1) 1 = the first sweep of a level
+ *                        visit does not read the zero start vector; 0 = zero it in
+ *                        memory.  Bit-identical.
+ *   mg_gs_diag_free      (plan, 0..2, default 1) row form of the Gauss-Seidel
+ *                        copies of stk_mg_create_from_csr (see there).  Rounding.
+ *   mg_fuse_restrict     (launch, 0..1, default 1) restricted residual as
+ *                        (R A) u - R f for plans that follow it (see
+ *                        stk_mg_set_option).  Rounding.
+ *   mg_restrict_one_pass (launch, 0..2, default 1) (R A) u - R f as one pass:
+ *                        1 = for matrices with per-slice coefficients, 2 = for
+ *                        every plan, 0 = never.  Bit-identical.
+ *   mg_fuse_coarse       (launch, 0..1, default 1) the coarse end of the V-cycle
+ *                        as one fused launch.  Bit-identical.
+ *   mg_coarse_lds        (launch, 0..1, default 1) the fused coarse end keeps its
+ *                        level vectors in LDS.  Bit-identical.
+ *   mg_coarse_uniform    (launch, 0..2, default 1) the LDS form on uniform ELL
+ *                        copies; 0 = on the levels' own copies; 2 = 512 threads
+ *                        throughout.  Bit-identical. */
 int stk_set_tuning(const char *key, int32_t value);
 
 /* ---- time slices of a slab (BlockDiagMPI._matvec with different operators per
@@ -348,8 +398,8 @@ typedef struct {
     const double *x, *x_lo, *x_hi;
 } stk_kron_ell_term;
 
-/* Tuning key (stk_set_tuning): "ell_wg_per_cu" (persistent workgroups per CU,
- * 0 = default).  K must be one of 5, 7, 9, 12, 16; at most 3 terms.
+/* Tuning key "ell_wg_per_cu" (stk_set_tuning).  K must be one of 5, 7, 9, 12,
+ * 16; at most 3 terms.
  * Terms with ghost rows (x_lo / x_hi) are handled as two launches: the
  * slab-local part, then stk_kron_ell_ghost_apply (with a copy of the old
  * boundary entries of y in between when beta != 0).  Every entry of y is
@@ -388,9 +438,8 @@ int stk_kron_ell_ghost_apply(void *stream, const stk_ell_pattern *pattern_host,
  * ghost time steps interleaved: ghosts[2*j] = x[j, t = -1] (X_loc_bdr[0],
  * mpi_vector.py:148-175), ghosts[2*j + 1] = x[j, t = n_loc] (X_loc_bdr[-1]);
  * a side without a neighbour is zero-filled.  K one of 5, 7, 9, 12, 16; at most
- * 3 terms; slabs of any size (64-bit addressing).
- * Tuning keys: "pack_wg_per_cu", "pack_flags" (bit 0: non-temporal stores of y,
- * bit 1: non-temporal loads of the slot stream). */
+ * 3 terms; slabs of any size (64-bit addressing).  The stores of y and the loads
+ * of the slot stream are non-temporal. */
 typedef struct {
     int32_t M, K;
     int32_t col_bits; /* 2^col_bits >= M */
@@ -576,13 +625,6 @@ int stk_kron_plan_boundary_apply(stk_kron_plan *plan, void *stream, int32_t n_lo
                                  const double *records, const double *x_lo,
                                  const double *x_hi, double *ghost_work, double *y);
 
-/* Diagnostic: while `buf` (device, at least 8 * grid * 4 words) is non-NULL,
- * the headline instantiation of the one-row form (2 terms, K = 7, no ghosts;
- * tuning key "pack_rows" = 1) runs a stamped build
- * that leaves, per wavefront, the shader-clock cycles spent in the four
- * segments of a row-group iteration.  NULL switches it off. */
-int stk_kron_pack_set_diag(unsigned long long *buf);
-
 /* ghosts[2*j] = lo[j], ghosts[2*j + 1] = hi[j] (a NULL side is written as
  * zero): brings the two received time rows into the layout above. */
 int stk_interleave_ghosts(void *stream, int32_t M, const double *lo,
@@ -620,8 +662,7 @@ typedef struct {
     int32_t diag_free;
 } stk_ell_rows;
 
-/* y = alpha * A(t) x + beta * z; x has x_rows rows, y and z have ell->n_rows.
- * Tuning key "rows_wg_per_cu". */
+/* y = alpha * A(t) x + beta * z; x has x_rows rows, y and z have ell->n_rows. */
 int stk_ell_spmm(void *stream, const stk_ell_rows *ell_host, int32_t n_loc,
                  int32_t ld, int32_t x_rows, double ca, const double *cm,
                  const double *x, double alpha, double beta, const double *z,
@@ -842,13 +883,12 @@ int stk_mg_smooth(stk_mg *mg, void *stream, int32_t level, int32_t n_loc,
  * ("fast_parts", 1) is the arithmetic the mirrored driver runs by default (r.Pr
  * histories within 1e-10 of the CPU path for 4 % of the solve); key 0 with
  * ("fuse_restrict", 0) has the reference's forms everywhere.
- * With coordinates, the bands of the strip-wise sweeps hold several mesh rows
- * (tuning key "mg_band_merge" as it stands when the plan is built; 0 = the default:
- * 6 for a family, 1 for a single matrix): inside a thicker band a stage walks mesh
+ * With coordinates, the bands of the strip-wise sweeps hold several mesh rows (6
+ * for a family, 1 for a single matrix): inside a thicker band a stage walks mesh
  * tiles instead of the level's full width (a family's P apply 2 % faster on slabs of
  * 17 time steps and more, bit-identical).
  * The host work runs on the threads of the library (STK_HOST_THREADS overrides
- * their number); STK_PLAN_TIMING=1 prints the seconds per stage on stderr. */
+ * their number). */
 typedef struct {
     int32_t n_rows, n_cols;
     const int32_t *indptr, *indices;
@@ -863,7 +903,7 @@ typedef struct {
  * inverse: the two planners' V-cycles are then equal bit for bit, not to 1e-13.
  * fn(n, a, inv, user): a and inv are n x n, row-major, HOST; returns 0 on success.
  * fn = NULL restores the built-in inverse.  Called on the thread that calls
- * stk_mg_create_from_csr.  The hook and the tuning key "mg_band_merge" are
+ * stk_mg_create_from_csr.  The hook and the tuning key "mg_gs_diag_free" are
  * process-wide; a plan construction reads both once, under a mutex, when it starts,
  * so a setter on another thread takes effect for constructions that start later and
  * never half way through one.  A caller that wants a hook for ONE construction while

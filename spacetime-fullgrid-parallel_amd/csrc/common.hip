@@ -21,6 +21,61 @@ extern "C" const char *stk_last_error(void) { return g_err; }
 
 extern "C" int stk_version(void) { return 200; }
 
+// ---- tuning keys (stk.h documents each one) ------------------------------------
+stk_tuning g_tuning;
+
+namespace {
+
+enum TuneKind { TUNE_LAUNCH, TUNE_PLAN, TUNE_COUNTER };
+
+struct TuneKey {
+    const char *name;
+    std::atomic<int32_t> stk_tuning::*field;
+    int32_t lo, hi;  // accepted values
+    TuneKind kind;   // read at every launch / when a plan is created / a counter (0 resets, n > 0 checks)
+};
+
+const TuneKey k_tune_keys[] = {
+    {"kron_block", &stk_tuning::kron_block, 0, 1024, TUNE_LAUNCH},
+    {"ell_wg_per_cu", &stk_tuning::ell_wg_per_cu, 0, 16, TUNE_LAUNCH},
+    {"ell_force_wide", &stk_tuning::ell_force_wide, 0, 1, TUNE_LAUNCH},
+    {"rows_force_wide", &stk_tuning::rows_force_wide, 0, 1, TUNE_LAUNCH},
+    {"pack_rows", &stk_tuning::pack_rows, 1, 2, TUNE_PLAN},
+    {"pack_multi_lanes", &stk_tuning::pack_multi_lanes, 0, 2, TUNE_LAUNCH},
+    {"pack_check_steps", &stk_tuning::pack_check_steps, 0, 1, TUNE_LAUNCH},
+    {"mg_strip_mb", &stk_tuning::mg_strip_mb, 0, 1 << 20, TUNE_LAUNCH},
+    {"mg_strip_width", &stk_tuning::mg_strip_width, 0, 1 << 10, TUNE_LAUNCH},
+    {"mg_strips_used", &stk_tuning::mg_strips_used, 0, INT32_MAX, TUNE_COUNTER},
+    {"mg_zero_start", &stk_tuning::mg_zero_start, 0, 1, TUNE_LAUNCH},
+    {"mg_gs_diag_free", &stk_tuning::mg_gs_diag_free, 0, 2, TUNE_PLAN},
+    {"mg_fuse_restrict", &stk_tuning::mg_fuse_restrict, 0, 1, TUNE_LAUNCH},
+    {"mg_restrict_one_pass", &stk_tuning::mg_restrict_one_pass, 0, 2, TUNE_LAUNCH},
+    {"mg_fuse_coarse", &stk_tuning::mg_fuse_coarse, 0, 1, TUNE_LAUNCH},
+    {"mg_coarse_lds", &stk_tuning::mg_coarse_lds, 0, 1, TUNE_LAUNCH},
+    {"mg_coarse_uniform", &stk_tuning::mg_coarse_uniform, 0, 2, TUNE_LAUNCH},
+};
+
+}  // namespace
+
+extern "C" int stk_set_tuning(const char *key, int32_t value)
+{
+    STK_REQUIRE(key != nullptr, "stk_set_tuning: null key");
+    for (const TuneKey &k : k_tune_keys) {
+        if (std::strcmp(key, k.name) != 0) continue;
+        STK_REQUIRE(value >= k.lo && value <= k.hi, "stk_set_tuning: %s=%d not in %d..%d", k.name, value, k.lo, k.hi);
+        std::atomic<int32_t> &v = g_tuning.*k.field;
+        if (k.kind == TUNE_COUNTER && value > 0) {
+            const int32_t n = v.load(std::memory_order_relaxed);
+            STK_REQUIRE(n >= value, "stk_set_tuning: %s: %d so far, %d required", k.name, n, value);
+            return 0;
+        }
+        v.store(value, std::memory_order_relaxed);
+        return 0;
+    }
+    stk_set_error("stk_set_tuning: unknown key '%s'", key);
+    return 2;
+}
+
 int stk_cu_count()
 {
     // per device (one process may drive several), queried once per device and thread

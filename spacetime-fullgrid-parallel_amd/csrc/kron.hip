@@ -18,18 +18,6 @@
 
 #include "stk_common.h"
 
-int stk_kron_ell_set_tuning(const char *key, int32_t value);  // kron_ell.hip
-int stk_kron_pack_set_tuning(const char *key, int32_t value);  // kron_pack.hip
-int stk_kron_pack_terms_set_tuning(const char *key, int32_t value);  // kron_pack_multi.hip
-extern int g_plan_pack_rows;                                   // plan.hip
-int stk_rows_ell_set_tuning(const char *key, int32_t value);  // rows_ell.hip
-int stk_wavelet_set_tuning(const char *key, int32_t value);   // wavelet.hip
-extern int g_mg_gs_diag_free;  // mg_build.hip
-extern int g_mg_restrict_one_pass;  // mg.hip
-extern int g_mg_coarse_static_fetch;  // mg_coarse.hip
-extern int g_mg_fuse_coarse, g_mg_coarse_max_rows, g_mg_fuse_restrict, g_mg_zero_start, g_mg_strip_mb, g_mg_strips_used, g_mg_strip_width;  // mg.hip
-extern int g_mg_coarse_pairs, g_mg_coarse_lds, g_mg_coarse_uniform;  // mg_coarse.hip
-
 namespace {
 
 constexpr int MAXE = 16;  // CSR entries per row staged in LDS (longer rows spill to global reads)
@@ -260,13 +248,11 @@ __global__ __launch_bounds__(BS) void kron_sum_kernel(const KronArgs<NT> a)
     }
 }
 
-int g_kron_bs = 0;  // 0 = choose by lane utilisation
-
 template <int NT, bool SHARED_IN>
 int launch_kron(hipStream_t st, const KronArgs<NT> &a_in)
 {
     KronArgs<NT> a = a_in;
-    int best = g_kron_bs;
+    int best = stk_tune(g_tuning.kron_block);  // 0 (or another value): choose by lane utilisation
     if (best != 256 && best != 512 && best != 1024) {
         // rows must not straddle workgroups (LDS time stencil): pick the block
         // size that wastes the fewest lanes, preferring smaller blocks
@@ -403,103 +389,6 @@ __global__ __launch_bounds__(SBS) void time_csr_kernel(int64_t total, int32_t M,
 }
 
 }  // namespace
-
-int g_stk_tuning_epoch = 0;  // captured V-cycle graphs (mg.hip) belong to the tuning state they were recorded under
-extern int g_mg_graph, g_mg_graph_replays;
-extern int g_mg_band_merge;  // mg_build.hip
-
-extern "C" int stk_set_tuning(const char *key, int32_t value)
-{
-    STK_REQUIRE(key != nullptr, "stk_set_tuning: null key");
-    if (std::strcmp(key, "mg_graph_replays") == 0) {  // tests: reset (0) / require at least `value` replays
-        if (value > 0 && g_mg_graph_replays < value) {
-            stk_set_error("mg_graph_replays: %d graph launches so far, %d required", g_mg_graph_replays, value);
-            return 2;
-        }
-        if (value == 0) g_mg_graph_replays = 0;
-        return 0;
-    }
-    ++g_stk_tuning_epoch;
-    if (std::strcmp(key, "mg_band_merge") == 0) {  // plans built by stk_mg_create_from_csr from now on
-        g_mg_band_merge = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_graph") == 0) {
-        g_mg_graph = value;
-        return 0;
-    }
-    if (std::strcmp(key, "kron_block") == 0) {
-        g_kron_bs = value;
-        return 0;
-    }
-    if (stk_kron_ell_set_tuning(key, value) == 0) return 0;
-    if (stk_kron_pack_set_tuning(key, value) == 0) return 0;
-    if (stk_kron_pack_terms_set_tuning(key, value) == 0) return 0;
-    if (stk_rows_ell_set_tuning(key, value) == 0) return 0;
-    if (stk_wavelet_set_tuning(key, value) == 0) return 0;
-    if (std::strcmp(key, "pack_rows") == 0) {  // plans created from now on: matrix rows per slot row (1 or 2)
-        g_plan_pack_rows = value >= 2 ? 2 : 1;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_strip_mb") == 0) {
-        g_mg_strip_mb = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_strip_width") == 0) {
-        g_mg_strip_width = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_coarse_static_fetch") == 0) {
-        g_mg_coarse_static_fetch = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_strips_used") == 0) {  // tests: reset (0) / require at least `value` strip launches
-        if (value > 0 && g_mg_strips_used < value) {
-            stk_set_error("mg_strips_used: %d strip launches so far, %d required", g_mg_strips_used, value);
-            return 2;
-        }
-        if (value == 0) g_mg_strips_used = 0;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_zero_start") == 0) {
-        g_mg_zero_start = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_gs_diag_free") == 0) {
-        g_mg_gs_diag_free = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_fuse_restrict") == 0) {
-        g_mg_fuse_restrict = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_coarse_max_rows") == 0) {
-        g_mg_coarse_max_rows = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_coarse_lds") == 0) {
-        g_mg_coarse_lds = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_restrict_one_pass") == 0) {
-        g_mg_restrict_one_pass = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_coarse_uniform") == 0) {
-        g_mg_coarse_uniform = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_coarse_pairs") == 0) {
-        g_mg_coarse_pairs = value;
-        return 0;
-    }
-    if (std::strcmp(key, "mg_fuse_coarse") == 0) {
-        g_mg_fuse_coarse = value;
-        return 0;
-    }
-    stk_set_error("stk_set_tuning: unknown key '%s'", key);
-    return 2;
-}
 
 extern "C" int stk_kron_sum_apply(void *stream, int32_t M, int32_t n_loc, int32_t ld, const int32_t *indptr,
                                   const int32_t *indices, const int32_t *row_ids, int32_t n_terms,

@@ -284,10 +284,6 @@ __global__ __launch_bounds__(BS, K >= 12 ? 4 : 6) void kron_ell_kernel(const Ell
     }
 }
 
-int g_ell_wg_per_cu = 0;
-int g_ell_force_wide = 0;     // testing: 64-bit addressing on small slabs
-int g_ell_force_generic = 0;  // benchmarking: run the generic kernel even when the fast path applies
-
 template <int NT, bool SHARED_IN, int K, bool GENERIC, bool WIDE = false>
 int launch4(hipStream_t st, const EllArgs<NT> &a, unsigned grid, size_t lds)
 {
@@ -310,8 +306,7 @@ template <int NT, bool SHARED_IN, int K>
 int launch3(hipStream_t st, const EllArgs<NT> &a, unsigned grid, size_t lds)
 {
     if (a.wide) return launch4<NT, SHARED_IN, K, true, true>(st, a, grid, lds);
-    const bool generic = a.ovf_indptr != nullptr || g_ell_force_generic;
-    return generic ? launch4<NT, SHARED_IN, K, true>(st, a, grid, lds)
+    return a.ovf_indptr != nullptr ? launch4<NT, SHARED_IN, K, true>(st, a, grid, lds)
                    : launch4<NT, SHARED_IN, K, false>(st, a, grid, lds);
 }
 
@@ -323,7 +318,7 @@ int launch2(hipStream_t st, const EllArgs<NT> &a_in, int K)
     if (a.R * K > 4 * BS) a.R = 4 * BS / K;  // at most 4 prefetched entries per thread
     a.ngroups = (a.M + a.R - 1) / a.R;
     a.chunk = (a.ngroups + 7) / 8;
-    a.wide = g_ell_force_wide || (int64_t)a.M * a.ld * 8 >= ((int64_t)1 << 32);
+    a.wide = stk_tune(g_tuning.ell_force_wide) || (int64_t)a.M * a.ld * 8 >= ((int64_t)1 << 32);
     a.vec_bytes = a.wide ? 0u : (uint32_t)((int64_t)a.M * a.ld * 8);
     const int KS = (K + 3) & ~3;
     const size_t lds = sizeof(double) * ((a.any_tri ? (size_t)NT * a.R * (a.n_loc + 3) : 0) +
@@ -332,7 +327,8 @@ int launch2(hipStream_t st, const EllArgs<NT> &a_in, int K)
                        sizeof(double) * (size_t)NT * 3 * (a.n_loc + 2) + 32;
     const int n_cu = stk_cu_count();
     // wide rows (K >= 12, e.g. the 15-point mass matrix of the cube) get 128 VGPRs: 2 workgroups per CU
-    int per_cu = g_ell_wg_per_cu > 0 ? g_ell_wg_per_cu : (K >= 12 ? 2 : 3);
+    const int wg_per_cu = stk_tune(g_tuning.ell_wg_per_cu);
+    int per_cu = wg_per_cu > 0 ? wg_per_cu : (K >= 12 ? 2 : 3);
     const int by_lds = (int)(160 * 1024 / (lds + 256));
     if (per_cu > by_lds) per_cu = by_lds > 0 ? by_lds : 1;
     int per_xcd = (n_cu / 8) * per_cu;
@@ -538,23 +534,6 @@ int dispatch(hipStream_t st, const stk_ell_pattern *pat, int32_t n_loc, int32_t 
 }
 
 }  // namespace
-
-int stk_kron_ell_set_tuning(const char *key, int32_t value)
-{
-    if (std::strcmp(key, "ell_force_wide") == 0) {
-        g_ell_force_wide = value;
-        return 0;
-    }
-    if (std::strcmp(key, "ell_force_generic") == 0) {
-        g_ell_force_generic = value;
-        return 0;
-    }
-    if (std::strcmp(key, "ell_wg_per_cu") == 0) {
-        g_ell_wg_per_cu = value;
-        return 0;
-    }
-    return 1;
-}
 
 extern "C" int stk_kron_ell_ghost_apply(void *stream, const stk_ell_pattern *pat, int32_t n_loc, int32_t ld,
                                         int32_t n_terms, const stk_kron_ell_term *t, double *y)

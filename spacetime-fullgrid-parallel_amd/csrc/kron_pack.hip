@@ -69,6 +69,8 @@
 
 namespace {
 
+constexpr int BS = 512;  // threads per workgroup of kron_pack_kernel
+
 template <int NT>
 struct PackArgs {
     const uint32_t *slots;   // [n_units][K]
@@ -85,7 +87,6 @@ struct PackArgs {
     int32_t ngroups, chunk;  // groups in total / per XCD
     int32_t col_bits, n_codes;
     int32_t flags;  // bit 0: non-temporal y stores, bit 1: non-temporal slot loads
-    unsigned long long *diag;  // DIAG instantiation: [waves][4] cycle sums
     // explicit values (no dictionary): [n_units][K][RP][NT], term k reads entry k
     const double *vals;
     int32_t n_mats;
@@ -97,26 +98,10 @@ typedef double stk_v2d __attribute__((ext_vector_type(2)));
 
 __device__ inline double2 load2(const char *p) { return *reinterpret_cast<const double2 *>(p); }
 
-// One stamp of the shader clock, ordered against the instruction stream (diagnostic
-// builds only; see the DIAG parameter below).
-__device__ inline unsigned long long stamp()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-
-// DIAG = true is a separate diagnostic instantiation (tools/kron_ab.py --phases): every
-// wave sums the shader-clock cycles it spends in the four segments of an
-// iteration -- publish + barrier, gathers + space factors, exchange + barrier,
-// time stencil + store -- into a.diag[wave][4].  Its outputs are still correct;
-// its run time is not quoted anywhere.
-template <int NT, int K, int NPF, bool GHOST, int BS, bool DIAG, int RP, bool DICT = true, bool MULTI = false>
+template <int NT, int K, int NPF, bool GHOST, int RP, bool DICT = true, bool MULTI = false>
 __global__ __launch_bounds__(BS, (K >= 12 || RP > 1) ? 4 : 6) void kron_pack_kernel(const PackArgs<NT> a)
 {
-    static_assert(!MULTI || (!GHOST && !DIAG && DICT), "inputs per term: no ghost lanes, dictionary form");
+    static_assert(!MULTI || (!GHOST && DICT), "inputs per term: no ghost lanes, dictionary form");
     constexpr int NPV = DICT ? 1 : 2;  // explicit values prefetched per thread (R is sized for it)
     constexpr int KS = (K + 3) & ~3;  // LDS stride of a row's slots (16-byte vectors)
     extern __shared__ double sm[];
@@ -224,9 +209,7 @@ __global__ __launch_bounds__(BS, (K >= 12 || RP > 1) ? 4 : 6) void kron_pack_ker
     };
     if (g < gend) fetch(g);
 
-    unsigned long long seg[4] = {0, 0, 0, 0}, ts = 0;
     for (; g < gend; g += step) {
-        if (DIAG) ts = stamp();
         const int rows = min(R, a.n_units - g * R);
         // ---- publish this group's entries ----------------------------------
 #pragma unroll
@@ -244,10 +227,6 @@ __global__ __launch_bounds__(BS, (K >= 12 || RP > 1) ? 4 : 6) void kron_pack_ker
         }
         if (tid < rows * RP) s_row[tid] = prow;
         __syncthreads();
-        if (DIAG) {
-            const unsigned long long t = stamp();
-            seg[0] += t - ts, ts = t;
-        }
         if (g + step < gend) fetch(g + step);  // in flight behind the gathers
 
         const bool active = in_row && r < rows;
@@ -312,24 +291,8 @@ __global__ __launch_bounds__(BS, (K >= 12 || RP > 1) ? 4 : 6) void kron_pack_ker
                     const uint4 v = so[u];
                     sl[4 * u] = v.x, sl[4 * u + 1] = v.y, sl[4 * u + 2] = v.z, sl[4 * u + 3] = v.w;
                 }
-                if constexpr (DIAG) {
-                    // ablations of the diagnostic build (wrong results, timing only):
-                    // 16: every slot gathers the row's own column (one line set per row,
-                    //     same instruction count); 32: one gather per lane instead of K
-                    if (a.flags & 16) {
 #pragma unroll
-                        for (int u = 0; u < K; ++u) sl[u] = (uint32_t)yrow[0];
-                    }
-                }
-                if (DIAG && (a.flags & 32)) {
-                    xv[0] = load2(base_lane + (size_t)(sl[0] & col_mask) * stride_lane);
-#pragma unroll
-                    for (int u = 1; u < K; ++u) xv[u] = xv[0];
-                } else {
-#pragma unroll
-                    for (int u = 0; u < K; ++u)
-                        xv[u] = load2(base_lane + (size_t)(sl[u] & col_mask) * stride_lane);
-                }
+                for (int u = 0; u < K; ++u) xv[u] = load2(base_lane + (size_t)(sl[u] & col_mask) * stride_lane);
             }
             // The slot words are read a second time for their codes rather than
             // kept in registers across the gathers (the offset is made opaque so
@@ -366,15 +329,6 @@ __global__ __launch_bounds__(BS, (K >= 12 || RP > 1) ? 4 : 6) void kron_pack_ker
             }
         }
 
-        if (DIAG) {
-            // the sums must exist before the stamp: make them opaque to the scheduler
-#pragma unroll
-            for (int j = 0; j < RP; ++j)
-#pragma unroll
-                for (int k = 0; k < NT; ++k) asm volatile("" : "+v"(acc0[j][k]), "+v"(acc1[j][k]));
-            const unsigned long long t = stamp();
-            seg[1] += t - ts, ts = t;
-        }
         // ---- time stencil through LDS, store ---------------------------------
         double y0[RP], y1[RP];
 #pragma unroll
@@ -393,10 +347,6 @@ __global__ __launch_bounds__(BS, (K >= 12 || RP > 1) ? 4 : 6) void kron_pack_ker
                 }
             }
             __syncthreads();
-            if (DIAG) {
-                const unsigned long long t = stamp();
-                seg[2] += t - ts, ts = t;
-            }
             if (active && !ghost_lane) {
 #pragma unroll
                 for (int k = 0; k < NT; ++k) {
@@ -459,16 +409,6 @@ __global__ __launch_bounds__(BS, (K >= 12 || RP > 1) ? 4 : 6) void kron_pack_ker
                 }
             }
         }
-        if (DIAG) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // charge the store to this segment
-            const unsigned long long t = stamp();
-            seg[3] += t - ts;
-        }
-    }
-    if (DIAG && a.diag != nullptr && (tid & 63) == 0) {
-        unsigned long long *d = a.diag + ((size_t)blockIdx.x * (BS / 64) + (tid >> 6)) * 4;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) d[q] = seg[q];
     }
 }
 
@@ -793,74 +733,56 @@ __global__ __launch_bounds__(256) void interleave_ghosts_kernel(int32_t M, const
         gh[j] = make_double2(lo ? lo[j] : 0.0, hi ? hi[j] : 0.0);
 }
 
-int g_pack_wg_per_cu = 0;
-int g_pack_flags = 3;  // non-temporal y stores and slot loads: measured 2-3 % faster at J_time = 6 / J_space = 9
-int g_pack_block = 512;                   // threads per workgroup: 512 or 256
-int g_pack_multi_lanes = 1;               // inputs per term: 0 = the terms take turns in one lane (round 4)
-int g_pack_multi_wg_per_cu = 0;           // inputs per term: workgroups per CU (0: as the one-input form)
-int g_pack_multi_r = 0;                   // inputs per term: cap on the slot rows of a group (0: none)
-int g_pack_check_steps = 0;               // inputs per term: verify the stated time steps against the factors (tests)
-unsigned long long *g_pack_diag = nullptr;  // set: the next headline-shape launch runs the DIAG instantiation
-
-template <int NT, int K, bool GHOST, int BS, int RP>
+template <int NT, int K, bool GHOST, int RP>
 int launch_npf(hipStream_t st, const PackArgs<NT> &a, unsigned grid, size_t lds)
 {
     const int npf = (a.R * K + BS - 1) / BS;
     if constexpr (RP == 2) {
         if (a.vals != nullptr) {  // explicit values: pairs only (the one-row plain form is kron_ell.hip)
             if (npf <= 1)
-                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 1, GHOST, BS, false, RP, false>), dim3(grid), dim3(BS), lds,
+                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 1, GHOST, RP, false>), dim3(grid), dim3(BS), lds,
                                    st, a);
             else if (npf <= 2)
-                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 2, GHOST, BS, false, RP, false>), dim3(grid), dim3(BS), lds,
+                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 2, GHOST, RP, false>), dim3(grid), dim3(BS), lds,
                                    st, a);
             else
-                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 4, GHOST, BS, false, RP, false>), dim3(grid), dim3(BS), lds,
+                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 4, GHOST, RP, false>), dim3(grid), dim3(BS), lds,
                                    st, a);
             STK_LAUNCH_CHECK();
             return 0;
         }
     }
-    if constexpr (!GHOST && NT >= 2 && BS == 512) {
+    if constexpr (!GHOST && NT >= 2) {
         if (a.xk[0] != nullptr) {  // inputs per term (dictionary form only: checked by the entry point)
             if (npf <= 1)
-                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 1, false, BS, false, RP, true, true>), dim3(grid), dim3(BS),
+                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 1, false, RP, true, true>), dim3(grid), dim3(BS),
                                    lds, st, a);
             else if (npf <= 2)
-                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 2, false, BS, false, RP, true, true>), dim3(grid), dim3(BS),
+                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 2, false, RP, true, true>), dim3(grid), dim3(BS),
                                    lds, st, a);
             else
-                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 4, false, BS, false, RP, true, true>), dim3(grid), dim3(BS),
+                hipLaunchKernelGGL((kron_pack_kernel<NT, K, 4, false, RP, true, true>), dim3(grid), dim3(BS),
                                    lds, st, a);
-            STK_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    if constexpr (NT == 2 && K == 7 && !GHOST && BS == 512 && RP == 1) {
-        if (a.diag != nullptr && npf <= 1) {
-            hipLaunchKernelGGL((kron_pack_kernel<NT, K, 1, GHOST, BS, true, RP>), dim3(grid), dim3(BS), lds, st, a);
             STK_LAUNCH_CHECK();
             return 0;
         }
     }
     if (npf <= 1)
-        hipLaunchKernelGGL((kron_pack_kernel<NT, K, 1, GHOST, BS, false, RP>), dim3(grid), dim3(BS), lds, st, a);
+        hipLaunchKernelGGL((kron_pack_kernel<NT, K, 1, GHOST, RP>), dim3(grid), dim3(BS), lds, st, a);
     else if (npf <= 2)
-        hipLaunchKernelGGL((kron_pack_kernel<NT, K, 2, GHOST, BS, false, RP>), dim3(grid), dim3(BS), lds, st, a);
+        hipLaunchKernelGGL((kron_pack_kernel<NT, K, 2, GHOST, RP>), dim3(grid), dim3(BS), lds, st, a);
     else
-        hipLaunchKernelGGL((kron_pack_kernel<NT, K, 4, GHOST, BS, false, RP>), dim3(grid), dim3(BS), lds, st, a);
+        hipLaunchKernelGGL((kron_pack_kernel<NT, K, 4, GHOST, RP>), dim3(grid), dim3(BS), lds, st, a);
     STK_LAUNCH_CHECK();
     return 0;
 }
 
-template <int NT, int BS, int RP>
+template <int NT, int RP>
 int launch(hipStream_t st, PackArgs<NT> a, int K)
 {
     const bool ghost = a.gh != nullptr;
     a.W = a.P + (ghost ? 1 : 0);
     a.R = BS / a.W;
-    const bool multi = a.xk[0] != nullptr;
-    if (multi && g_pack_multi_r > 0 && a.R > g_pack_multi_r) a.R = g_pack_multi_r;
     if (a.R * K > 4 * BS) a.R = 4 * BS / K;  // at most 4 prefetched words per thread
     if (a.vals && a.R * K * RP * NT > 2 * BS) a.R = 2 * BS / (K * RP * NT);  // ... and 2 values
     STK_REQUIRE(a.R >= 1, "stk_kron_pack_apply: a slot row of %d x %d x %d values is too wide", K, RP, NT);
@@ -874,13 +796,11 @@ int launch(hipStream_t st, PackArgs<NT> a, int K)
     while (a.R > 1 && lds_of(a.R) > 64 * 1024) --a.R;  // short slabs: many units per group
     a.ngroups = (a.n_units + a.R - 1) / a.R;
     a.chunk = (a.ngroups + 7) / 8;
-    a.flags = g_pack_flags;
-    a.diag = g_pack_diag;
+    a.flags = 3;  // non-temporal y stores and slot loads: measured 2-3 % faster at J_time = 6 / J_space = 9
     const size_t lds = lds_of(a.R);
     STK_REQUIRE(lds <= 64 * 1024, "stk_kron_pack_apply: %zu bytes of LDS per workgroup (dictionary too large?)", lds);
     const int n_cu = stk_cu_count();
-    int per_cu = g_pack_wg_per_cu > 0 ? g_pack_wg_per_cu : ((K >= 12 || RP > 1) ? 2 : 3) * (512 / BS);
-    if (multi && g_pack_multi_wg_per_cu > 0) per_cu = g_pack_multi_wg_per_cu;
+    int per_cu = (K >= 12 || RP > 1) ? 2 : 3;
     const int by_lds = (int)(160 * 1024 / (lds + 256));
     if (per_cu > by_lds) per_cu = by_lds > 0 ? by_lds : 1;
     int per_xcd = (n_cu / 8) * per_cu;
@@ -889,8 +809,8 @@ int launch(hipStream_t st, PackArgs<NT> a, int K)
     const unsigned grid = (unsigned)per_xcd * 8;
 #define STK_PACK_CASE(KK)                                                   \
     case KK:                                                                \
-        return ghost ? launch_npf<NT, KK, true, BS, RP>(st, a, grid, lds)   \
-                     : launch_npf<NT, KK, false, BS, RP>(st, a, grid, lds);
+        return ghost ? launch_npf<NT, KK, true, RP>(st, a, grid, lds)       \
+                     : launch_npf<NT, KK, false, RP>(st, a, grid, lds);
     if constexpr (RP == 1) {
         switch (K) {
             STK_PACK_CASE(5)
@@ -940,46 +860,10 @@ int dispatch(hipStream_t st, const stk_pack_pattern *pat, int32_t n_loc, int32_t
         if (t[k].tri) a.any_tri = 1;
     }
     a.P = (n_loc + 1) / 2;
-    if (pat->rows_per_unit == 2) return launch<NT, 512, 2>(st, a, pat->K);
-    // 256-thread workgroups: only where a row still fits comfortably
-    if (g_pack_block == 256 && a.P + 1 <= 64 && !xs) return launch<NT, 256, 1>(st, a, pat->K);
-    return launch<NT, 512, 1>(st, a, pat->K);
+    return pat->rows_per_unit == 2 ? launch<NT, 2>(st, a, pat->K) : launch<NT, 1>(st, a, pat->K);
 }
 
 }  // namespace
-
-int stk_kron_pack_set_tuning(const char *key, int32_t value)
-{
-    if (std::strcmp(key, "pack_wg_per_cu") == 0) {
-        g_pack_wg_per_cu = value;
-        return 0;
-    }
-    if (std::strcmp(key, "pack_flags") == 0) {
-        g_pack_flags = value;
-        return 0;
-    }
-    if (std::strcmp(key, "pack_multi_wg_per_cu") == 0) {
-        g_pack_multi_wg_per_cu = value;
-        return 0;
-    }
-    if (std::strcmp(key, "pack_multi_r") == 0) {
-        g_pack_multi_r = value;
-        return 0;
-    }
-    if (std::strcmp(key, "pack_multi_lanes") == 0) {
-        g_pack_multi_lanes = value;
-        return 0;
-    }
-    if (std::strcmp(key, "pack_check_steps") == 0) {
-        g_pack_check_steps = value;
-        return 0;
-    }
-    if (std::strcmp(key, "pack_block") == 0) {
-        g_pack_block = value == 256 ? 256 : 512;
-        return 0;
-    }
-    return 1;
-}
 
 extern "C" int stk_kron_pack_apply(void *stream, const stk_pack_pattern *pat, int32_t n_loc, int32_t ld,
                                    int32_t n_terms, const stk_kron_pack_term *t, const double *x,
@@ -1064,7 +948,7 @@ extern "C" int stk_kron_pack_apply_multi_steps(void *stream, const stk_pack_patt
     }
     STK_REQUIRE(((uintptr_t)y & 15) == 0, "stk_kron_pack_apply_multi: y must be 16-byte aligned");
     hipStream_t st = stk_stream(stream);
-    if (g_pack_check_steps && t_begin_host) {
+    if (stk_tune(g_tuning.pack_check_steps) && t_begin_host) {
         // Tuning key "pack_check_steps" (tests, debugging): a stated range that omits a
         // time step the factor reads would silently drop its contribution (the lanes of
         // that step are never launched).  Column s of a factor is read through sub[s + 1],
@@ -1092,8 +976,9 @@ extern "C" int stk_kron_pack_apply_multi_steps(void *stream, const stk_pack_patt
     // A lane group per term pays where the slab is long or does not fit the Infinity
     // Cache; on short slabs of small problems the turn-taking lanes are level or ahead in
     // a loop of launches and level inside S (profiles/r05_multi_lanes_vs_turns.log).
-    const bool lanes = g_pack_multi_lanes == 2 ||
-                       (g_pack_multi_lanes == 1 && (n_loc >= 24 || (int64_t)pat->M * ld * 8 > ((int64_t)256 << 20)));
+    const int multi_lanes = stk_tune(g_tuning.pack_multi_lanes);
+    const bool lanes = multi_lanes == 2 ||
+                       (multi_lanes == 1 && (n_loc >= 24 || (int64_t)pat->M * ld * 8 > ((int64_t)256 << 20)));
     if (lanes) {
         const int rc = stk_kron_pack_terms_launch(st, pat, n_loc, ld, n_terms, t, xs_host, t_begin_host, t_end_host,
                                                   beta, y);
@@ -1117,15 +1002,6 @@ extern "C" int stk_interleave_ghosts(void *stream, int32_t M, const double *lo, 
     hipLaunchKernelGGL(interleave_ghosts_kernel, dim3(stk_flat_grid(M, 256)), dim3(256), 0, stk_stream(stream), M, lo,
                        hi, reinterpret_cast<double2 *>(ghosts));
     STK_LAUNCH_CHECK();
-    return 0;
-}
-
-/* Diagnostic (tools/kron_ab.py --phases): while `buf` is set, launches of the headline
- * instantiation (2 terms, K = 7, no ghosts) run the stamped build and leave
- * per-wave cycle sums of the four segments of an iteration in buf[wave][4]. */
-extern "C" int stk_kron_pack_set_diag(unsigned long long *buf)
-{
-    g_pack_diag = buf;
     return 0;
 }
 

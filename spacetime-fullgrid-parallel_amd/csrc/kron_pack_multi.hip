@@ -264,10 +264,6 @@ __global__ __launch_bounds__(BS, 4) void kron_pack_terms_kernel(const TermArgs<N
     }
 }
 
-int g_terms_wg_per_cu = 0;  // 0: two workgroups per CU
-int g_terms_flags = 3;
-int g_terms_r = 0;  // cap on the slot rows of a group (0: as many as 512 lanes hold)
-
 template <int NT, int K, int RP>
 int launch_npf(hipStream_t st, const TermArgs<NT> &a, unsigned grid, size_t lds)
 {
@@ -286,7 +282,6 @@ template <int NT, int RP>
 int launch(hipStream_t st, TermArgs<NT> a, int K)
 {
     a.R = BS / a.W;
-    if (g_terms_r > 0 && a.R > g_terms_r) a.R = g_terms_r;
     if (a.R * K > 4 * BS) a.R = 4 * BS / K;  // at most 4 prefetched words per thread
     const int KS = (K + 3) & ~3;
     auto lds_of = [&](int R) {
@@ -297,10 +292,10 @@ int launch(hipStream_t st, TermArgs<NT> a, int K)
     while (a.R > 1 && lds_of(a.R) > 64 * 1024) --a.R;
     a.ngroups = (a.n_units + a.R - 1) / a.R;
     a.chunk = (a.ngroups + 7) / 8;
-    a.flags = g_terms_flags;
+    a.flags = 3;  // non-temporal y stores and slot loads, as in kron_pack.hip
     const size_t lds = lds_of(a.R);
     STK_REQUIRE(lds <= 64 * 1024, "stk_kron_pack_apply_multi: %zu bytes of LDS per workgroup", lds);
-    int per_cu = g_terms_wg_per_cu > 0 ? g_terms_wg_per_cu : 2;
+    int per_cu = 2;
     const int by_lds = (int)(160 * 1024 / (lds + 256));
     if (per_cu > by_lds) per_cu = by_lds > 0 ? by_lds : 1;
     int per_xcd = (stk_cu_count() / 8) * per_cu;
@@ -373,23 +368,6 @@ int dispatch(hipStream_t st, const stk_pack_pattern *pat, int32_t n_loc, int32_t
 }
 
 }  // namespace
-
-int stk_kron_pack_terms_set_tuning(const char *key, int32_t value)
-{
-    if (std::strcmp(key, "terms_wg_per_cu") == 0) {
-        g_terms_wg_per_cu = value;
-        return 0;
-    }
-    if (std::strcmp(key, "terms_r") == 0) {
-        g_terms_r = value;
-        return 0;
-    }
-    if (std::strcmp(key, "terms_flags") == 0) {
-        g_terms_flags = value;
-        return 0;
-    }
-    return 1;
-}
 
 // Shared with kron_pack.hip (stk_kron_pack_apply_multi): arguments already checked there.
 // Returns -1 when fewer than two slot rows would fit a workgroup (more than 256 lanes per slot row).

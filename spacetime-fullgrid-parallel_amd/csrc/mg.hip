@@ -97,14 +97,8 @@ __global__ __launch_bounds__(GBS) void coarse_kernel(int32_t n0, int32_t n_loc, 
 
 }  // namespace
 
-int g_mg_strip_width = 2;       // least width of a strip in units of (sweeps x groups) bands
-int g_mg_strip_mb = 250;        // strip-wise smoothing: working set (u and f) of a strip in MB; 0 = off
-                                // (measured at J_time=6/J_space=9: 120 -> 250 MB is 4.5 % on S and P, 400 the same)
-int g_mg_zero_start = 1;        // 0: zero u in memory and run the first sweep like the others
-int g_mg_fuse_restrict = 1;     // 0: residual and restriction as two steps
-int g_mg_restrict_one_pass = 1; // 0: (R A) u - R f as two passes of the row engine
-int g_mg_fuse_coarse = 1;       // 0 disables the fused coarse sub-V-cycle
-int g_mg_coarse_max_rows = 4096;  // levels up to this many rows may be fused (larger ones fill the GPU by themselves)
+// levels up to this many rows may be fused into the coarse sub-V-cycle (larger ones fill the GPU by themselves)
+constexpr int64_t COARSE_MAX_ROWS = 4096;
 
 struct EllLevel {
     bool has_a = false, has_gs = false, has_p = false, has_r = false, has_ra = false, has_alt = false;
@@ -146,21 +140,6 @@ struct stk_mg {
     // residual also take the fast forms (the post-smoothing never does)
     int fast_parts = 0;
     int strip_pct = 100;  // this plan's strips as a percentage of the tuning key "mg_strip_mb"
-    // recorded V-cycle applications (see g_mg_graph)
-    struct Recorded {
-        const double *f, *cm;
-        double *u;
-        const int32_t *kind;
-        int32_t n_loc, ld;
-        double ca;
-        int epoch, fuse_restrict;
-        hipGraphExec_t exec;  // NULL: seen once, not recorded yet
-        bool refused;         // capture failed: stays on the plain path
-        uint64_t last_use;
-    };
-    std::vector<Recorded> recorded;
-    hipStream_t capture_stream = nullptr;
-    uint64_t clock = 0;
 };
 
 // The ELL row engine needs 16-byte time pairs (even ld) and slabs below 64 GiB.
@@ -175,7 +154,7 @@ static inline bool ell_slab_ok(int64_t rows, int ld)
 static bool can_zero_start(const stk_mg *mg, int level, int ld)
 {
     const EllLevel &E = mg->ell[level];
-    return g_mg_zero_start && level >= 1 && mg->smoothsteps >= 1 && E.has_gs && !E.fwd0.empty() &&
+    return stk_tune(g_tuning.mg_zero_start) && level >= 1 && mg->smoothsteps >= 1 && E.has_gs && !E.fwd0.empty() &&
            E.fwd0.size() + 1 == E.fwd_pos.size() && ell_slab_ok(mg->lv[level].n, ld);
 }
 
@@ -201,24 +180,19 @@ static bool can_zero_start(const stk_mg *mg, int level, int ld)
 static const std::vector<int32_t> *strip_table(const EllLevel &E, bool backward, int64_t rows, int ld, int its,
                                                double strip_mb)
 {
-    const double g_mg_strip_mb = strip_mb;  // the process-wide strip size scaled by the plan's strip_pct
-    static const bool debug = getenv("STK_DEBUG_STRIPS") != nullptr;
-    if (debug)
-        fprintf(stderr, "strip_table: rows=%lld ld=%d its=%d bands=%d strip_mb=%g width=%d groups=%d\n",
-                (long long)rows, ld, its, E.n_tile_rows, g_mg_strip_mb, g_mg_strip_width,
-                (int)(backward ? E.bwd_pos : E.fwd_pos).size() - 1);
-    if (g_mg_strip_mb <= 0 || E.n_tile_rows < 2 || its < 1) return nullptr;
+    if (strip_mb <= 0 || E.n_tile_rows < 2 || its < 1) return nullptr;
     const double level_mb = 2.0 * (double)rows * ld * 8.0 / 1.0e6;  // u and f
-    int S = (int)(level_mb / g_mg_strip_mb + 0.999);
+    int S = (int)(level_mb / strip_mb + 0.999);
     const std::vector<int32_t> &pos = backward ? E.bwd_pos : E.fwd_pos;
     const int ng = (int)pos.size() - 1;
     const int Q = its * ng;
     // Strips partition the axis band + stage, 0 .. T + Q - 2.  Any width is
     // correct; a strip touches its own bands plus the skew of its Q stages, so it
-    // should be a few times wider than Q (g_mg_strip_width: in units of Q; tests
-    // set 0 to force many thin strips).
+    // should be a few times wider than Q (tuning key mg_strip_width: in units of Q;
+    // tests set 0 to force many thin strips).
     const int T = E.n_tile_rows, span = T + Q - 1;
-    const int min_width = g_mg_strip_width > 0 ? g_mg_strip_width * Q : 2;
+    const int strip_width = stk_tune(g_tuning.mg_strip_width);
+    const int min_width = strip_width > 0 ? strip_width * Q : 2;
     if (S > span / min_width) S = span / min_width;
     if (S < 2) return nullptr;
     auto &cache = backward ? E.bwd_strips : E.fwd_strips;
@@ -241,22 +215,6 @@ static const std::vector<int32_t> *strip_table(const EllLevel &E, bool backward,
     return &cache.emplace(key, std::move(tab)).first->second;
 }
 
-int g_mg_strips_used = 0;  // launches that came from a strip table (tests read it through stk_set_tuning)
-// Tuning key "mg_graph" (default 0): a V-cycle application that comes back with
-// the same operands (PCG iterations do: the same slabs, coefficients and tables
-// every time) is recorded into a hipGraph on its second occurrence and replayed
-// from then on.  One multigrid apply is ~300 dependent launches; on short slabs
-// (the shapes of an 8-GPU run: 8 or 9 time steps) they are only a few
-// microseconds each.  MEASURED (profiles/r03_op_graph*.log, ROCm 7.2, one
-// MI355X): replay is bit-identical and SLOWER than plain launches -- S 4.11 ->
-// 4.42 ms, P 5.56 -> 6.24 ms on 9-step slabs, 17.8 -> 18.3 / 21.3 -> 22.1 ms on
-// 65-step slabs: the host already enqueues faster than the GPU retires (the
-// recursion is C++), and a graph node costs the GPU about a microsecond more than
-// a plain dependent launch.  Kept as an option for hosts with slow launch paths.
-int g_mg_graph = 0;
-int g_mg_graph_replays = 0;  // graph launches so far (tests read it through stk_set_tuning)
-extern int g_stk_tuning_epoch;  // kron.hip: bumped by every stk_set_tuning
-
 static int smooth_level(stk_mg *mg, hipStream_t st, int level, int n_loc, int ld, double ca, const double *cm,
                         int its, bool backward, const double *f, double *u, bool zero_start = false, int cycle = 1 << 30)
 {
@@ -269,7 +227,7 @@ static int smooth_level(stk_mg *mg, hipStream_t st, int level, int n_loc, int ld
         const int ng = (int)pos.size() - 1;
         const bool zs = zero_start && !backward && its >= 1;
         const std::vector<int32_t> *strips =
-            strip_table(E, backward, L.n, ld, its, g_mg_strip_mb * (mg->strip_pct / 100.0));
+            strip_table(E, backward, L.n, ld, its, stk_tune(g_tuning.mg_strip_mb) * (mg->strip_pct / 100.0));
         const int S = strips ? (int)(strips->size() / (2 * (size_t)ng * its)) : 1;
         const int Q = its * ng;
         for (int s = 0; s < S; ++s)
@@ -277,7 +235,7 @@ static int smooth_level(stk_mg *mg, hipStream_t st, int level, int n_loc, int ld
                 const int g = q % ng;
                 const int p0 = strips ? (*strips)[((size_t)s * Q + q) * 2] : pos[g];
                 const int p1 = strips ? (*strips)[((size_t)s * Q + q) * 2 + 1] : pos[g + 1];
-                if (strips) ++g_mg_strips_used;
+                if (strips) g_tuning.mg_strips_used.fetch_add(1, std::memory_order_relaxed);
                 int rc;
                 if (zs && q < ng) {
                     // first sweep of a level visit: u is NOT initialised.  Group 0
@@ -317,7 +275,7 @@ static int mgm(stk_mg *mg, hipStream_t st, int j, int n_loc, int ld, double ca, 
                const int32_t *kind, const double *f_j, double *u_j, bool u_zero, int cycle)
 {
     const stk_mg_level &L = mg->lv[j];
-    if (g_mg_fuse_coarse && mg->coarse && j == mg->Lc && (ld & 1) == 0 && f_j == mg->f[j] && u_j == mg->u[j]) {
+    if (stk_tune(g_tuning.mg_fuse_coarse) && mg->coarse && j == mg->Lc && (ld & 1) == 0 && f_j == mg->f[j] && u_j == mg->u[j]) {
         // (the job list starts from zero itself when its vectors live in LDS;
         // the global-memory variant reads u)
         if (u_zero && !stk_coarse_plan_in_lds(mg->coarse))
@@ -351,7 +309,7 @@ static int mgm(stk_mg *mg, hipStream_t st, int j, int n_loc, int ld, double ca, 
     double *r_j = mg->r[j], *d_c = mg->f[j - 1], *u_c = mg->u[j - 1];
     const EllLevel &E = mg->ell[j];
     const bool even = ell_slab_ok(L.n, ld);
-    const bool fuse_restrict = (mg->fuse_restrict >= 0 ? mg->fuse_restrict != 0 : g_mg_fuse_restrict != 0) &&
+    const bool fuse_restrict = (mg->fuse_restrict >= 0 ? mg->fuse_restrict != 0 : stk_tune(g_tuning.mg_fuse_restrict) != 0) &&
                                ((j >= mg->fuse_min_level && j <= mg->fuse_max_level) || cycle < mg->fast_until_cycle ||
                                 (mg->fast_parts & 2));
     if (fuse_restrict && E.has_ra && E.has_r && even) {
@@ -362,7 +320,8 @@ static int mgm(stk_mg *mg, hipStream_t st, int j, int n_loc, int ld, double ca, 
         // family: P 5.54 -> 5.39 ms on 9-step slabs, 21.7 -> 21.5 ms on 65); K's plans, which run
         // two at a time inside S, measure SLOWER with it (S 3.31 -> 3.37 ms, 16.9 -> 17.2 ms:
         // profiles/r04_restrict_one_pass_ab.log).  Key 2: every plan.
-        rc = (g_mg_restrict_one_pass && E.ra_rows_as_r && (cm != nullptr || g_mg_restrict_one_pass >= 2))
+        const int one_pass = stk_tune(g_tuning.mg_restrict_one_pass);
+        rc = (one_pass && E.ra_rows_as_r && (cm != nullptr || one_pass >= 2))
                  ? stk_rows_ell2_launch(st, &E.ra, &E.r, n_loc, ld, L.n, C.n, ca, cm, u_j, f_j, d_c)
                  : -1;
         if (rc == -1) {
@@ -505,7 +464,7 @@ extern "C" int stk_mg_create(int32_t n_levels, const stk_mg_level *levels, int32
         for (int j = 1; j < n_levels - 1; ++j) {
             const EllLevel &E = mg->ell[j];
             arena_rows += 3 * (int64_t)mg->lv[j].n;
-            if (mg->lv[j].n > g_mg_coarse_max_rows || arena_rows * (int64_t)sizeof(double) > 144 * 1024 ||
+            if (mg->lv[j].n > COARSE_MAX_ROWS || arena_rows * (int64_t)sizeof(double) > 144 * 1024 ||
                 !(E.has_a && E.has_gs && E.has_p && E.has_r))
                 break;
             Lc = j;
@@ -565,9 +524,6 @@ void stk_mg_adopt(stk_mg *mg, void *const *dev_ptrs, int n)
 extern "C" int stk_mg_destroy(stk_mg *mg)
 {
     if (!mg) return 0;
-    for (auto &r : mg->recorded)
-        if (r.exec) (void)hipGraphExecDestroy(r.exec);
-    if (mg->capture_stream) (void)hipStreamDestroy(mg->capture_stream);
     for (void *p : mg->adopted) (void)hipFree(p);
     for (double *p : mg->u) (void)hipFree(p);
     for (double *p : mg->f) (void)hipFree(p);
@@ -580,10 +536,6 @@ extern "C" int stk_mg_destroy(stk_mg *mg)
 extern "C" int stk_mg_set_option(stk_mg *mg, const char *key, int32_t value)
 {
     STK_REQUIRE(mg && key, "stk_mg_set_option: null pointer");
-    // recorded V-cycles (tuning key mg_graph) were captured under the old options
-    for (auto &r : mg->recorded)
-        if (r.exec) (void)hipGraphExecDestroy(r.exec);
-    mg->recorded.clear();
     if (std::strcmp(key, "fuse_restrict") == 0) {
         mg->fuse_restrict = value < 0 ? -1 : (value != 0);
         return 0;
@@ -613,40 +565,6 @@ extern "C" int stk_mg_set_option(stk_mg *mg, const char *key, int32_t value)
     return 2;
 }
 
-static int run_vcycles(stk_mg *mg, hipStream_t st, int32_t n_loc, int32_t ld, double ca, const double *cm,
-                       const int32_t *kind, const double *f, double *u)
-{
-    const int J = (int)mg->lv.size() - 1;
-    for (int v = 0; v < mg->vcycles; ++v) {
-        int rc = mgm(mg, st, J, n_loc, ld, ca, cm, kind, f, u, /*u_zero=*/v == 0, v);  // multigrid.py:187
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-// Records run_vcycles into an executable graph (on a stream of the plan's own:
-// the caller's may be the legacy default stream, which cannot be captured).
-static hipGraphExec_t record_vcycles(stk_mg *mg, int32_t n_loc, int32_t ld, double ca, const double *cm,
-                                     const int32_t *kind, const double *f, double *u)
-{
-    if (!mg->capture_stream &&
-        hipStreamCreateWithFlags(&mg->capture_stream, hipStreamNonBlocking) != hipSuccess) {
-        mg->capture_stream = nullptr;
-        return nullptr;
-    }
-    if (hipStreamBeginCapture(mg->capture_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
-    const int rc = run_vcycles(mg, mg->capture_stream, n_loc, ld, ca, cm, kind, f, u);
-    hipGraph_t graph = nullptr;
-    const hipError_t end = hipStreamEndCapture(mg->capture_stream, &graph);
-    hipGraphExec_t exec = nullptr;
-    if (rc == 0 && end == hipSuccess && graph != nullptr &&
-        hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess)
-        exec = nullptr;
-    if (graph) (void)hipGraphDestroy(graph);
-    (void)hipGetLastError();
-    return exec;
-}
-
 extern "C" int stk_mg_apply(stk_mg *mg, void *stream, int32_t n_loc, int32_t ld, double ca, const double *cm,
                             const int32_t *kind, const double *f, double *u)
 {
@@ -657,42 +575,12 @@ extern "C" int stk_mg_apply(stk_mg *mg, void *stream, int32_t n_loc, int32_t ld,
     STK_REQUIRE(cm == nullptr || mg->lv[0].vals_m != nullptr, "stk_mg_apply: cm given but plan has no vals_m");
     STK_REQUIRE(ca != 0.0 || cm, "stk_mg_apply: zero matrix");
     hipStream_t st = stk_stream(stream);
-    if (g_mg_graph && !g_stk_timing) {
-        stk_mg::Recorded *hit = nullptr;
-        for (auto &r : mg->recorded)
-            if (r.f == f && r.u == u && r.cm == cm && r.kind == kind && r.n_loc == n_loc && r.ld == ld && r.ca == ca &&
-                r.epoch == g_stk_tuning_epoch && r.fuse_restrict == mg->fuse_restrict) {
-                hit = &r;
-                break;
-            }
-        if (hit == nullptr) {
-            // first occurrence: remembered, run on the plain path (one-off calls
-            // are never recorded)
-            stk_mg::Recorded fresh{f, cm, u, kind, n_loc, ld, ca, g_stk_tuning_epoch, mg->fuse_restrict, nullptr, false,
-                                   ++mg->clock};
-            if (mg->recorded.size() >= 24) {
-                size_t oldest = 0;
-                for (size_t k = 1; k < mg->recorded.size(); ++k)
-                    if (mg->recorded[k].last_use < mg->recorded[oldest].last_use) oldest = k;
-                if (mg->recorded[oldest].exec) (void)hipGraphExecDestroy(mg->recorded[oldest].exec);
-                mg->recorded[oldest] = fresh;
-            } else {
-                mg->recorded.push_back(fresh);
-            }
-        } else {
-            hit->last_use = ++mg->clock;
-            if (hit->exec == nullptr && !hit->refused) {
-                hit->exec = record_vcycles(mg, n_loc, ld, ca, cm, kind, f, u);
-                hit->refused = hit->exec == nullptr;
-            }
-            if (hit->exec != nullptr) {
-                STK_HIP(hipGraphLaunch(hit->exec, st));
-                ++g_mg_graph_replays;
-                return 0;
-            }
-        }
+    const int J = (int)mg->lv.size() - 1;
+    for (int v = 0; v < mg->vcycles; ++v) {
+        int rc = mgm(mg, st, J, n_loc, ld, ca, cm, kind, f, u, /*u_zero=*/v == 0, v);  // multigrid.py:187
+        if (rc) return rc;
     }
-    return run_vcycles(mg, st, n_loc, ld, ca, cm, kind, f, u);
+    return 0;
 }
 
 extern "C" int stk_mg_smooth(stk_mg *mg, void *stream, int32_t level, int32_t n_loc, int32_t ld, double ca,

@@ -12,7 +12,6 @@
 // planner (source/multigrid.py) builds the same plan with NumPy / SciPy; tests
 // compare V-cycles from the two.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -23,13 +22,10 @@
 #include <mutex>
 #include <numeric>
 #include <queue>
-#include <string>
 #include <thread>
 #include <vector>
 
 #include "stk_common.h"
-
-int g_mg_band_merge = 0;  // tuning key "mg_band_merge": mesh rows per band of the strip-wise sweeps (0 = default)
 
 namespace {
 
@@ -371,8 +367,6 @@ static const int ROW_SLOTS[] = {2, 4, 5, 6, 7, 9, 12, 16, 20};
 // the former below -- with stk_mg_set_option(plan, "fuse_restrict_max_level", finest - 1),
 // ("fast_until_cycle", vcycles - 1) and ("fast_parts", 1) the arithmetic of
 // HeatEquationMPI(arithmetic='accurate'), DESIGN.md section 5.
-int g_mg_gs_diag_free = 1;
-
 namespace {
 
 // sliced-ELL copy of the rows `order` of a union pattern (source/linop.py
@@ -440,8 +434,8 @@ bool ell_rows(Builder &B, const Union &u, const std::vector<int32_t> &order, boo
 
 Union union_of(const Csr &m) { return make_union(m, nullptr); }
 
-// The caller's own dense inverse (stk_mg_set_coarse_inverse), or none; the mesh rows per
-// band (tuning key "mg_band_merge").  Both are process-wide settings that a plan
+// The caller's own dense inverse (stk_mg_set_coarse_inverse), or none; the row form of
+// the sweeps (tuning key "mg_gs_diag_free").  Both are process-wide settings that a plan
 // construction reads ONCE, under the mutex, when it starts (PlannerSettings): a setter
 // running on another thread while plans are being built (this repository builds K's and
 // the family's plan side by side) cannot change a construction half way.
@@ -452,13 +446,13 @@ std::mutex g_planner_mutex;
 struct PlannerSettings {
     stk_dense_inverse_fn inverse_fn;
     void *inverse_user;
-    int band_merge;
+    int gs_diag_free;
 };
 
 PlannerSettings planner_settings()
 {
     std::lock_guard<std::mutex> lock(g_planner_mutex);
-    return PlannerSettings{g_inverse_fn, g_inverse_user, g_mg_band_merge};
+    return PlannerSettings{g_inverse_fn, g_inverse_user, stk_tune(g_tuning.mg_gs_diag_free)};
 }
 
 // dense inverse by Gauss-Jordan elimination with partial pivoting (level 0 is tiny)
@@ -521,17 +515,6 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
     STK_REQUIRE(!coords_host || (dim >= 1 && dim <= 3), "stk_mg_create_from_csr: dim=%d not in 1..3", dim);
     const int J = n_levels - 1;
     const PlannerSettings settings = planner_settings();  // one consistent view for this construction
-    // STK_PLAN_TIMING=1: seconds per stage of the planner on stderr
-    static const bool timing = getenv("STK_PLAN_TIMING") != nullptr;
-    std::map<std::string, double> spent;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto t_last = now();
-    auto lap = [&](const char *what) {
-        if (!timing) return;
-        const auto t = now();
-        spent[what] += std::chrono::duration<double>(t - t_last).count();
-        t_last = t;
-    };
     // ---- Galerkin hierarchies, coarse to fine (multigrid.py:142-145) -------------
     std::vector<Csr> A(n_levels), Mm(M_fine ? n_levels : 0), P(J), R(J);
     A[J] = from_host(*A_fine);
@@ -548,7 +531,6 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
         sort_rows(P[j]);
         R[j] = transpose(P[j]);
     }
-    lap("copy in, sort rows");
     // The chain of Galerkin products runs beside the plan of the finest level, which
     // needs nothing of it.  Worker threads work on the caller's device.
     int device = 0;
@@ -609,7 +591,6 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
             dia_a_of_row[i] = u.va[diag[i]];
             if (M_fine) dia_m_of_row[i] = u.vm[diag[i]];
         }
-        lap("union pattern, CSR upload");
         if (j == 0) return 0;
         // processing order (mesh tiles if coordinates are known) and bands
         const std::vector<int32_t> &tile = tile_of(n);
@@ -643,21 +624,14 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
         });
         std::vector<int64_t> rank(n);
         for (int p = 0; p < n; ++p) rank[tile[p]] = p;
-        lap("tile order");
         std::vector<int32_t> band = coupling_bands(coords_host, dim, u);
-        // several mesh rows per band for the strip-wise sweeps (tuning key "mg_band_merge" as
-        // it stands when the plan is built; 0 = the default: 6 for families a(t) = ca A +
-        // cm[t] M, 1 otherwise -- source/multigrid.py BAND_MERGE has the measurements):
+        // several mesh rows per band for the strip-wise sweeps: 6 for families a(t) = ca A +
+        // cm[t] M, 1 otherwise (source/multigrid.py BAND_MERGE has the measurements);
         // coarser bands keep "coupled rows at most one band apart", results do not change
-        if (coords_host && !band.empty()) {
-            const int merge = settings.band_merge > 0 ? settings.band_merge : (M_fine ? 6 : 1);
-            if (merge > 1)
-                for (auto &b : band) b /= merge;
-        }
-        lap("bands");
+        if (coords_host && !band.empty() && M_fine)
+            for (auto &b : band) b /= 6;
         auto key = [&](int i) { return (band.empty() ? (int64_t)0 : (int64_t)band[i] * n) + rank[i]; };
         bool ells_ok = ell_rows(B, u, tile, false, 0, nullptr, nullptr, &K.a);
-        lap("ELL copy of the level matrix");
         std::vector<std::vector<int32_t>> fwd_groups;
         for (int bw = 0; bw < 2; ++bw) {
             // depth in the dependency DAG of the sweep in dof order (row i waits for
@@ -686,7 +660,6 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
                 rows.insert(rows.end(), g.begin(), g.end());
                 ptr.push_back((int32_t)rows.size());
             }
-            lap("sweep schedules");
             // ELL copy: each group band by band, tile order inside a band
             std::vector<int32_t> listed, trow;
             for (auto &g : groups) {
@@ -695,22 +668,20 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
             }
             if (!band.empty())
                 for (int i : listed) trow.push_back(band[i]);
-            lap("sweep orders");
             stk_ell_rows *dst = bw ? &K.bwd : &K.fwd;
             // row form of this level's sweeps: diagonal-free (key 1, and the levels below
             // the finest with key 2) or with the diagonal (key 0; the finest level with
             // key 2, which also gets the diagonal-free copies as its alternative form)
-            const bool full_rows = g_mg_gs_diag_free == 0 || (g_mg_gs_diag_free == 2 && j == J);
+            const bool full_rows = settings.gs_diag_free == 0 || (settings.gs_diag_free == 2 && j == J);
             if (!full_rows) {
                 ells_ok = ell_rows(B, u, listed, true, 0, nullptr, nullptr, dst) && ells_ok;
             } else {
                 ells_ok = ell_rows(B, u, listed, false, 0, &dia_a_of_row, M_fine ? &dia_m_of_row : nullptr, dst) && ells_ok;
-                if (g_mg_gs_diag_free == 2) {
+                if (settings.gs_diag_free == 2) {
                     stk_ell_rows *alt = bw ? &K.bwd_alt : &K.fwd_alt;
                     if (ell_rows(B, u, listed, true, 0, nullptr, nullptr, alt)) (bw ? L.ell_bwd_alt : L.ell_fwd_alt) = alt;
                 }
             }
-            lap("ELL copies of the sweeps");
             if (bw) {
                 K.bwd_ptr = ptr;
                 K.bwd_trow = trow;
@@ -728,7 +699,6 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
         L.bwd_ptr_host = K.bwd_ptr.data();
         ells_ok = transfers.get() && ells_ok;
         const bool ra_ok = products.get();
-        lap("waiting for transfers and R A products");
         if (!ells_ok) return 0;
         L.ell_a = &K.a;
         L.ell_fwd = &K.fwd;
@@ -782,13 +752,11 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
                 if (ok0) L.ell_fwd0 = K.fwd0.data();
             }
         }
-        lap("zero-start copies");
         return 0;
     };
     {
         int rc = build_level(J);
         chain.join();
-        lap("waiting for the Galerkin products");
         for (int j = J - 1; j >= 0 && rc == 0; --j) rc = build_level(j);
         if (rc) {
             for (void *d : B.dev) (void)hipFree(d);
@@ -828,12 +796,5 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
     }
     stk_mg_adopt(mg, B.dev.data(), (int)B.dev.size());
     *out = mg;
-    lap("coarse inverses, stk_mg_create");
-    if (timing) {
-        double total = 0.0;
-        for (auto &kv : spent) total += kv.second;
-        fprintf(stderr, "stk_mg_create_from_csr: %.3f s\n", total);
-        for (auto &kv : spent) fprintf(stderr, "   %-36s %.3f s\n", kv.first.c_str(), kv.second);
-    }
     return 0;
 }

@@ -393,7 +393,7 @@ __global__ void repack_uniform_kernel(int n_rows, int K_src, int KU, const int32
     }
 }
 
-template <int KU, bool HAS_M, bool PAIR, int UBS, bool SF>
+template <int KU, bool HAS_M, bool PAIR, int UBS>
 __global__ __launch_bounds__(UBS) void mg_coarse_uniform_kernel(const CoarseArgs a, const UniArgs m)
 {
     typedef TimeElem<PAIR> E;
@@ -455,14 +455,10 @@ __global__ __launch_bounds__(UBS) void mg_coarse_uniform_kernel(const CoarseArgs
             const double2 v = pa[q];
             S.va[2 * q] = v.x, S.va[2 * q + 1] = v.y;
         }
-        // Every array is read whatever the job needs of it (the second value array and the
-        // diagonals of a transfer are zeros in the uniform copies): the SAME loads for every
-        // row, so that the compiler's wait counters know how many loads lie between a set of
-        // registers and the next one.  With loads behind branches it waited for vmcnt(0)
-        // before the first use of a prefetched row -- i.e. also for the set it had just issued
-        // for the job after next -- and a job took one L2 round trip, 1.35 us, whatever its
-        // rows (round 6).
-        if (HAS_M && (SF || (j.flags & 1))) {
+        // Only the arrays the job needs.  (Reading every array for every row -- the same
+        // loads whatever the job, so that the compiler's wait counters need not fall back to
+        // vmcnt(0) -- was measured and dropped: DESIGN.md section 3.4 and Appendix A.)
+        if (HAS_M && (j.flags & 1)) {
             const double2 *pm = reinterpret_cast<const double2 *>((mem ? m.vmem + mem1 * KU : m.vm) + e0);
 #pragma unroll
             for (int q = 0; q < KU / 2; ++q) {
@@ -470,22 +466,15 @@ __global__ __launch_bounds__(UBS) void mg_coarse_uniform_kernel(const CoarseArgs
                 S.vm[2 * q] = v.x, S.vm[2 * q + 1] = v.y;
             }
         }
-        if (SF || j.kind == JOB_GS) {
+        if (j.kind == JOB_GS) {
             S.da = (mem ? m.dmem + mem0 : m.dia_a)[row];
-            if (HAS_M && (SF || (j.flags & 1))) S.dm = (mem ? m.dmem + mem1 : m.dia_m)[row];
+            if (HAS_M && (j.flags & 1)) S.dm = (mem ? m.dmem + mem1 : m.dia_m)[row];
         }
         S.orow = m.row[row];
     };
-    // the first row of a thread in job jn -- or, where there is none (no row job, a thread
-    // beyond the job's rows, past the last job), row 0 of the uniform arrays: same loads
-    // (SF = false: loads only where there is a row -- round 4's form, kept for the A/B)
+    // the first row of a thread in job jn, where there is one
     auto fetch = [&](int jn, RowRegs &S) {
-        if constexpr (SF) {
-            CJob nj = s_jobs[min(jn, a.n_jobs - 1)];
-            const bool rows = jn < a.n_jobs && (nj.kind == JOB_SPMM || nj.kind == JOB_GS) && tid < nj.n_rows;
-            if (!rows) nj.mat_off = 0, nj.flags = 0;
-            load_row(nj, rows ? tid : 0, S);
-        } else if (jn < a.n_jobs) {
+        if (jn < a.n_jobs) {
             const CJob nj = s_jobs[jn];
             if ((nj.kind == JOB_SPMM || nj.kind == JOB_GS) && tid < nj.n_rows) load_row(nj, tid, S);
         }
@@ -595,10 +584,6 @@ __global__ __launch_bounds__(UBS) void mg_coarse_uniform_kernel(const CoarseArgs
 }
 
 }  // namespace
-
-int g_mg_coarse_pairs = 0;  // time pairs per workgroup (0 = default: 1, vectors resident in LDS)
-int g_mg_coarse_lds = 1;    // 0: keep the level vectors in global memory
-int g_mg_coarse_uniform = 1;  // 0: the LDS variant on the levels' own ELL copies (per-job slot counts)
 
 // Host side: the job list of MGM(Lc, u_Lc, f_Lc) and its launcher (used by mg.hip).
 struct stk_coarse_plan {
@@ -948,40 +933,30 @@ stk_coarse_plan *stk_coarse_plan_build(const stk_coarse_level *lv, int Lc, int s
 // need not zero it in memory.
 bool stk_coarse_plan_in_lds(const stk_coarse_plan *p)
 {
-    return g_mg_coarse_lds && g_mg_coarse_pairs <= 1 && sizeof(double) * (size_t)p->lds_rows <= 144 * 1024;
-}
-
-int g_mg_coarse_static_fetch = 0;  // tuning key "mg_coarse_static_fetch": the same loads for every row (A/B)
-
-template <int KU, bool HAS_M, bool PAIR, int UBS, bool SF>
-static int launch_uniform_sf(dim3 grid, size_t lds, hipStream_t st, const CoarseArgs &a, const UniArgs &m)
-{
-    static bool attr_set = false;  // per instantiation
-    if (!attr_set) {
-        STK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mg_coarse_uniform_kernel<KU, HAS_M, PAIR, UBS, SF>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((mg_coarse_uniform_kernel<KU, HAS_M, PAIR, UBS, SF>), grid, dim3(UBS), lds, st, a, m);
-    STK_LAUNCH_CHECK();
-    return 0;
+    return stk_tune(g_tuning.mg_coarse_lds) && sizeof(double) * (size_t)p->lds_rows <= 144 * 1024;
 }
 
 template <int KU, bool HAS_M, bool PAIR, int UBS>
 static int launch_uniform_one(dim3 grid, size_t lds, hipStream_t st, const CoarseArgs &a, const UniArgs &m)
 {
-    return g_mg_coarse_static_fetch ? launch_uniform_sf<KU, HAS_M, PAIR, UBS, true>(grid, lds, st, a, m)
-                                    : launch_uniform_sf<KU, HAS_M, PAIR, UBS, false>(grid, lds, st, a, m);
+    static bool attr_set = false;  // per instantiation
+    if (!attr_set) {
+        STK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mg_coarse_uniform_kernel<KU, HAS_M, PAIR, UBS>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((mg_coarse_uniform_kernel<KU, HAS_M, PAIR, UBS>), grid, dim3(UBS), lds, st, a, m);
+    STK_LAUNCH_CHECK();
+    return 0;
 }
 
 // 1024 threads per time step where the registers allow: a level-5 job is then one or
 // four rows per thread instead of two or eight.
-extern int g_mg_coarse_uniform;
 static int launch_uniform(int KU, bool has_m, bool pair, dim3 grid, size_t lds, hipStream_t st, const CoarseArgs &a,
                           const UniArgs &m)
 {
     if (KU == 8) {
-        if (g_mg_coarse_uniform == 2) {  // A/B: 512 threads throughout
+        if (stk_tune(g_tuning.mg_coarse_uniform) == 2) {  // A/B: 512 threads throughout
             if (has_m) return pair ? launch_uniform_one<8, true, true, 512>(grid, lds, st, a, m)
                                    : launch_uniform_one<8, true, false, 512>(grid, lds, st, a, m);
             return pair ? launch_uniform_one<8, false, true, 512>(grid, lds, st, a, m)
@@ -1008,7 +983,7 @@ int stk_coarse_plan_run(const stk_coarse_plan *p, hipStream_t st, int n_loc, int
     a.n_jobs = p->n_jobs;
     a.n_loc = n_loc;
     a.ld = ld;
-    a.pairs_per_wg = g_mg_coarse_pairs > 0 ? g_mg_coarse_pairs : 1;
+    a.pairs_per_wg = 1;
     a.ca = ca;
     a.cm = cm;
     a.kind = cm ? kind : nullptr;
@@ -1041,7 +1016,7 @@ int stk_coarse_plan_run(const stk_coarse_plan *p, hipStream_t st, int n_loc, int
         const bool pair = lds_pair <= lds_max;
         const dim3 grid(pair ? all_pairs : n_loc);
         const size_t lds = pair ? lds_pair : lds_one;
-        if (g_mg_coarse_uniform && p->KU != 0 && (!cm || p->uni_has_m)) {
+        if (stk_tune(g_tuning.mg_coarse_uniform) && p->KU != 0 && (!cm || p->uni_has_m)) {
             UniArgs m;
             m.jobs = p->dev_cjobs;
             m.idx = p->u_idx;
@@ -1067,7 +1042,7 @@ int stk_coarse_plan_run(const stk_coarse_plan *p, hipStream_t st, int n_loc, int
         STK_LAUNCH_CHECK();
         return 0;
     }
-    const unsigned grid = (unsigned)((all_pairs + a.pairs_per_wg - 1) / a.pairs_per_wg);
+    const unsigned grid = (unsigned)all_pairs;  // one time pair per workgroup
     if (cm)
         hipLaunchKernelGGL(mg_coarse_kernel<true>, dim3(grid), dim3(CBS), 0, st, a);
     else

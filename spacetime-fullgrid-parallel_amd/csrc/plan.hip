@@ -20,6 +20,7 @@
 
 struct stk_kron_plan {
     int32_t M = 0, K = 0, n_mats = 0;
+    int pack_rows = 2;  // tuning key "pack_rows" when the plan was created: matrix rows per slot row (1 or 2)
     bool packed = false;
     // plain ELL form
     stk_ell_pattern ell{};
@@ -38,8 +39,6 @@ struct stk_kron_plan {
     std::vector<void *> owned;  // every device allocation
     int64_t nnz_union = 0;
 };
-
-int g_plan_pack_rows = 2;  // tuning key "pack_rows": matrix rows per slot row of the packed form (1 or 2)
 
 // Slots of a unit of up to `rp` rows with K slots each (the instantiations of
 // csrc/kron_pack.hip); 0: no such form.
@@ -188,7 +187,7 @@ int build_explicit_pairs(stk_kron_plan *p, int32_t M, int K, int n_mats, int col
                          const std::vector<int32_t> &row_ids, const std::vector<std::vector<double>> &ell_val)
 {
     const int rp = 2, K2 = stk_pack_unit_slots(K, rp);
-    if (K2 == 0 || g_plan_pack_rows < 2) return 0;
+    if (K2 == 0 || p->pack_rows < 2) return 0;
     std::vector<int32_t> perm(M);
     if (stk_pack_match_order(M, K, counts.data(), ell_idx.data(), row_ids.data(), K2, 8192, perm.data())) return 1;
     std::vector<int32_t> cnt2(M), idx2((size_t)M * K), own2(M), ent2((size_t)M * K);
@@ -356,7 +355,7 @@ int build(stk_kron_plan *p, int32_t M, int32_t n_mats, const int32_t *const *ind
     p->packed = true;
     // ---- several rows per slot row (stk_pack_group_rows above; source/linop.py
     // calls the same function) -----------------------------------------------------
-    const int rp = g_plan_pack_rows;
+    const int rp = p->pack_rows;
     const int K2 = stk_pack_unit_slots(K, rp);
     if (K2 == 0 || rp < 2) return 0;
     uint32_t zero_code = (uint32_t)n_codes;  // the tuple "no entry": +0.0 in every matrix
@@ -436,6 +435,7 @@ extern "C" int stk_kron_plan_create(int32_t M, int32_t n_mats, const int32_t *co
             STK_REQUIRE(indices_host[m][e] >= 0 && indices_host[m][e] < M,
                         "stk_kron_plan_create: matrix %d has column %d outside 0..%d", m, indices_host[m][e], M - 1);
     stk_kron_plan *p = new stk_kron_plan();
+    p->pack_rows = stk_tune(g_tuning.pack_rows);
     const int rc = build(p, M, n_mats, indptr_host, indices_host, data_host, row_order_host);
     if (rc) {
         stk_kron_plan_destroy(p);

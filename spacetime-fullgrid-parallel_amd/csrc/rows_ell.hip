@@ -398,11 +398,7 @@ int launch2_npf(hipStream_t st, const Rows2Args &b, unsigned grid, size_t lds)
     return 0;
 }
 
-int g_rows_wg_per_cu = 0;
-int g_rows_force_wide = 0;  // testing: 64-bit addressing on small slabs
-int g_rows_alternate = 1;   // alternate the walking direction between launches
-int g_rows_nt_store = 1;    // bit 0: SPMM passes, bit 1: Gauss-Seidel groups, bit 2: the two-matrix pass
-unsigned g_rows_launch_count = 0;
+unsigned g_rows_launch_count = 0;  // the walking direction alternates between launches
 
 template <int MODE, int K, bool HAS_M, bool WIDE>
 int launch_npf_w(hipStream_t st, const RowsArgs &a, unsigned grid, size_t lds)
@@ -449,27 +445,6 @@ int launch_k(hipStream_t st, const RowsArgs &a, int K, unsigned grid, size_t lds
 
 }  // namespace
 
-int stk_rows_ell_set_tuning(const char *key, int32_t value)
-{
-    if (std::strcmp(key, "rows_force_wide") == 0) {
-        g_rows_force_wide = value;
-        return 0;
-    }
-    if (std::strcmp(key, "rows_alternate") == 0) {
-        g_rows_alternate = value;
-        return 0;
-    }
-    if (std::strcmp(key, "rows_nt_store") == 0) {
-        g_rows_nt_store = value;
-        return 0;
-    }
-    if (std::strcmp(key, "rows_wg_per_cu") == 0) {
-        g_rows_wg_per_cu = value;
-        return 0;
-    }
-    return 1;
-}
-
 // Shared launcher (also used by mg.hip).  mode: 0 = SPMM, 1 = GS.
 int stk_rows_ell_launch(hipStream_t st, int mode, const stk_ell_rows *e, int32_t pos_begin, int32_t pos_end,
                         int32_t n_loc, int32_t ld, int64_t x_rows, int64_t y_rows, double ca, const double *cm,
@@ -507,12 +482,12 @@ int stk_rows_ell_launch(hipStream_t st, int mode, const stk_ell_rows *e, int32_t
     if (a.R * e->K > 4 * BS) a.R = 4 * BS / e->K;  // at most 4 prefetched entries per thread
     a.ngroups = (pos_end - pos_begin + a.R - 1) / a.R;
     a.chunk = (a.ngroups + 7) / 8;
-    a.reverse = g_rows_alternate ? (int)(g_rows_launch_count++ & 1u) : 0;
+    a.reverse = (int)(g_rows_launch_count++ & 1u);
     a.zero_own = (zero_own || e->diag_free) ? 1 : 0;  // diagonal-free rows: u_i = (f_i - sum_{j != i}) / a_ii
-    a.wide = g_rows_force_wide || x_rows * ld * 8 >= ((int64_t)1 << 32) || y_rows * ld * 8 >= ((int64_t)1 << 32);
+    a.wide = stk_tune(g_tuning.rows_force_wide) || x_rows * ld * 8 >= ((int64_t)1 << 32) || y_rows * ld * 8 >= ((int64_t)1 << 32);
     a.x_bytes = a.wide ? 0u : (uint32_t)(x_rows * ld * 8);
     a.y_bytes = a.wide ? 0u : (uint32_t)(y_rows * ld * 8);
-    a.nt_store = (g_rows_nt_store >> (mode == MODE_GS ? 1 : 0)) & 1;
+    a.nt_store = mode == MODE_GS ? 0 : 1;  // non-temporal stores in the SPMM passes only
     if (mode == MODE_GS) STK_REQUIRE(e->dia_a && (!cm || e->dia_m), "rows_ell: GS needs the diagonal arrays");
     const int K = e->K;
     const int KS = (K + 3) & ~3;
@@ -522,7 +497,7 @@ int stk_rows_ell_launch(hipStream_t st, int mode, const stk_ell_rows *e, int32_t
     const size_t lds = 2 * buf_doubles * sizeof(double) + 16;
     const int n_cu = stk_cu_count();
     // wide rows (K >= 12) get 128 VGPRs: 2 workgroups per CU
-    int per_cu = g_rows_wg_per_cu > 0 ? g_rows_wg_per_cu : (K >= 12 ? 2 : 3);
+    int per_cu = K >= 12 ? 2 : 3;
     int per_xcd = (n_cu / 8) * per_cu;
     if (per_xcd > a.chunk) per_xcd = a.chunk;
     if (per_xcd < 1) per_xcd = 1;
@@ -570,12 +545,12 @@ int stk_rows_ell2_launch(hipStream_t st, const stk_ell_rows *e, const stk_ell_ro
     if (a.R * K > 4 * BS) a.R = 4 * BS / K;  // at most 4 prefetched entries per thread and matrix
     a.ngroups = (e->n_pos + a.R - 1) / a.R;
     a.chunk = (a.ngroups + 7) / 8;
-    a.reverse = g_rows_alternate ? (int)(g_rows_launch_count++ & 1u) : 0;
+    a.reverse = (int)(g_rows_launch_count++ & 1u);
     a.zero_own = 0;
-    a.wide = g_rows_force_wide || x_rows * ld * 8 >= ((int64_t)1 << 32) || y_rows * ld * 8 >= ((int64_t)1 << 32);
+    a.wide = stk_tune(g_tuning.rows_force_wide) || x_rows * ld * 8 >= ((int64_t)1 << 32) || y_rows * ld * 8 >= ((int64_t)1 << 32);
     a.x_bytes = a.wide ? 0u : (uint32_t)(x_rows * ld * 8);
     a.y_bytes = a.wide ? 0u : (uint32_t)(y_rows * ld * 8);
-    a.nt_store = (g_rows_nt_store >> 2) & 1;
+    a.nt_store = 0;
     b.idx2 = e2->idx;
     b.va2 = e2->va;
     b.x2 = x2;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 
 #include "stk.h"
@@ -29,6 +30,31 @@ void stk_set_error(const char *fmt, ...);
     } while (0)
 
 static inline hipStream_t stk_stream(void *s) { return (hipStream_t)s; }
+
+// Process-wide tuning values: the keys of stk_set_tuning (table in common.hip, meanings
+// in stk.h).  Set from any host thread; read with relaxed loads (stk_tune), the
+// plan-time keys once per plan construction.
+struct stk_tuning {
+    std::atomic<int32_t> kron_block{0};
+    std::atomic<int32_t> ell_wg_per_cu{0};
+    std::atomic<int32_t> ell_force_wide{0};
+    std::atomic<int32_t> rows_force_wide{0};
+    std::atomic<int32_t> pack_rows{2};
+    std::atomic<int32_t> pack_multi_lanes{1};
+    std::atomic<int32_t> pack_check_steps{0};
+    std::atomic<int32_t> mg_strip_mb{250};
+    std::atomic<int32_t> mg_strip_width{2};
+    std::atomic<int32_t> mg_strips_used{0};  // counter: launches that came from a strip table
+    std::atomic<int32_t> mg_zero_start{1};
+    std::atomic<int32_t> mg_gs_diag_free{1};
+    std::atomic<int32_t> mg_fuse_restrict{1};
+    std::atomic<int32_t> mg_restrict_one_pass{1};
+    std::atomic<int32_t> mg_fuse_coarse{1};
+    std::atomic<int32_t> mg_coarse_lds{1};
+    std::atomic<int32_t> mg_coarse_uniform{1};
+};
+extern stk_tuning g_tuning;
+static inline int32_t stk_tune(const std::atomic<int32_t> &v) { return v.load(std::memory_order_relaxed); }
 
 // Per-operation device-time counters of the C ABI (stk_timing_*, common.hip; the
 // counterpart of LinearOperatorMPI.time_applies, reference mpi_kron.py:23-36): a

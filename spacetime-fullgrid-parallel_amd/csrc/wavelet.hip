@@ -225,18 +225,7 @@ int launch_reg(hipStream_t st, int32_t M, int transposed, const double *x, doubl
     return 0;
 }
 
-int g_wavelet_variant = 0;  // 0 = automatic, 1 = LDS kernel only
-
 }  // namespace
-
-int stk_wavelet_set_tuning(const char *key, int32_t value)
-{
-    if (std::strcmp(key, "wavelet_variant") == 0) {
-        g_wavelet_variant = value;
-        return 0;
-    }
-    return 1;
-}
 
 extern "C" int stk_wavelet_apply(void *stream, int32_t M, int32_t J, int32_t ld, int32_t transposed,
                                  const double *x, double *y)
@@ -247,7 +236,7 @@ extern "C" int stk_wavelet_apply(void *stream, int32_t M, int32_t J, int32_t ld,
     STK_REQUIRE(ld >= N, "stk_wavelet_apply: ld=%d < 2^J+1=%d", ld, N);
     STK_REQUIRE(x && y, "stk_wavelet_apply: null pointer");
     STK_REQUIRE(N <= TILE_ELEMS, "stk_wavelet_apply: J too large");
-    if (g_wavelet_variant == 0 && J >= 1 && J <= 7 && ld == N + 1 &&
+    if (J >= 1 && J <= 7 && ld == N + 1 &&
         (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
         hipStream_t st = stk_stream(stream);
         switch (J) {

@@ -380,10 +380,9 @@ class HeatEquationMPI:
                 kinv = pool.submit(timed('plan of K', on_dev(MultiGrid)), self.A_x, hierarchy,
                                    smoothsteps=smoothsteps, vcycles=vcycles, gs_rows=gs_rows)
                 # bands of 6 mesh rows for the family's strip-wise sweeps on longer slabs
-                # (source/multigrid.py BAND_MERGE: P -2 %, bit-identical); an
-                # environment override serves the A/B
+                # (source/multigrid.py BAND_MERGE: P -2 %, bit-identical)
                 n_steps_ = self.dofs_distr.t_end - self.dofs_distr.t_begin
-                merge = None if 'STK_BAND_MERGE_FAMILY' in os.environ else (6 if n_steps_ >= 16 else 1)
+                merge = 6 if n_steps_ >= 16 else 1
                 members = pool.submit(
                     timed('plan of the family', on_dev(MultiGridFamily)), self.A_x, self.M_x, hierarchy, ca=alpha,
                     cms=[2**j for j in range(self.J_time + 1)],

@@ -148,10 +148,7 @@ def _restrict(mat, fd):
 
 
 def _rows_per_tile(rows_per_tile):
-    import os
-    if rows_per_tile is None:
-        rows_per_tile = int(os.environ.get('STK_ROWS_PER_TILE', '2048'))
-    return rows_per_tile
+    return 2048 if rows_per_tile is None else rows_per_tile
 
 
 # point sets of at least this many dofs are ordered by libstk's host threads
@@ -172,8 +169,7 @@ def tile_order_from_coords(coords, rows_per_tile=None, small_lexsort=True):
     ext = np.maximum(hi - lo, 1e-30)
     ntiles = max(1.0, len(p) / float(rows_per_tile))
     side = (np.prod(ext) / ntiles)**(1.0 / d)
-    snake = os.environ.get('STK_TILE_WALK') == 'snake' and d == 2
-    if len(p) >= TILE_ORDER_ON_HOST_THREADS and d in (2, 3) and not snake and __package__:
+    if len(p) >= TILE_ORDER_ON_HOST_THREADS and d in (2, 3) and __package__:
         # the same order on the host threads of libstk (stk_tile_order: a sample sort;
         # tests/test_host_cpu.py test_plan_helpers_on_host_threads).  Not when this file
         # is loaded alone, without its package (the fixture generator under tests/golden)
@@ -186,13 +182,6 @@ def tile_order_from_coords(coords, rows_per_tile=None, small_lexsort=True):
         return order
     tiles = tuple(np.floor((p[:, k] - lo[k]) / side).astype(np.int64)
                   for k in range(d))
-    if snake:
-        # EXPERIMENT (measured and not adopted):
-        # a boustrophedon walk inside a tile -- every other mesh row of a tile from right to
-        # left, so that the two readers of a gathered row above / below sit closer together
-        ys = np.unique(p[:, 1])
-        row = np.searchsorted(ys, p[:, 1])
-        lex = (np.where(row & 1, -p[:, 0], p[:, 0]), p[:, 1])
     return np.lexsort(lex + tiles).astype(np.int32)
 
 

@@ -19,7 +19,6 @@ one, sums and products of them do too, and a whole PCG solve then stays in HBM
 (heateq.py: solve()).
 """
 import ctypes
-import os
 import threading
 import weakref
 
@@ -740,7 +739,7 @@ class PackedEllMatrices:
     free bits can name, a slot count without a pair instantiation); the caller
     then keeps the plain form."""
     MAX_CODES = 512  # dictionary entries (codes x rows per unit) in LDS next to the exchange buffers
-    ROWS_PER_UNIT = int(os.environ.get('STK_PACK_ROWS', '2'))
+    ROWS_PER_UNIT = 2
 
     def __init__(self, M, K, ell_idx, ell_vals, row_ids, has_overflow,
                  counts=None, own=None, rows_per_unit=1):

@@ -406,7 +406,7 @@ def coupling_bands(coords, indptr, indices, rows_of=None, coord_band=None):
 
 
 # Mesh rows per band of the strip-wise sweeps (constructor argument `band_merge` of
-# MultiGrid / MultiGridFamily; None = these defaults).  coupling_bands gives the thinnest
+# MultiGrid / MultiGridFamily; None = this default).  coupling_bands gives the thinnest
 # bands the coupling allows (single mesh rows on a structured mesh); the rows of a
 # dependency group are listed band by band and in tile order inside a band.  With one
 # mesh row per band a stage walks the level's full width before it comes back to the row
@@ -418,8 +418,7 @@ def coupling_bands(coords, indptr, indices, rows_of=None, coord_band=None):
 # and 26.0 -> 25.5 ms on config 5's 17-step slab with 4-8 rows per band, 5.36 -> 5.41 ms at
 # 9 steps; K's plans (two chains side by side inside S) gain nothing.  HeatEquationMPI
 # asks for 6 rows per band in the family's plan from 16 time steps on.
-BAND_MERGE = int(__import__('os').environ.get('STK_BAND_MERGE', '1'))
-BAND_MERGE_FAMILY = int(__import__('os').environ.get('STK_BAND_MERGE_FAMILY', str(BAND_MERGE)))
+BAND_MERGE = 1
 
 # Gauss-Seidel rows on the device: True = diagonal-free copies,
 # u_i = (f_i - sum_{j != i} a_ij u_j) / a_ii (PETSc MatSOR's form; one gather less
@@ -448,7 +447,7 @@ class _DeviceHierarchy:
         assert gs_rows in (None, 'free', 'full', 'owned')
         self.gs_rows = gs_rows
         if band_merge is None:
-            band_merge = BAND_MERGE_FAMILY if mat_m is not None else BAND_MERGE
+            band_merge = BAND_MERGE
         self.band_merge = max(1, int(band_merge))
         self.J = hierarchy.J
         self.smoothsteps, self.vcycles = smoothsteps, vcycles

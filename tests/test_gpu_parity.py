@@ -2309,54 +2309,6 @@ def test_two_stream_multigrid_pair_is_exact(stk):
         assert np.array_equal(p_two_memset, p_one), J_time
 
 
-def test_recorded_vcycles_replay_exactly(stk):
-    """A multigrid application that recurs with the same operands can be recorded
-    into a hipGraph on its second occurrence and replayed afterwards (tuning key
-    "mg_graph", csrc/mg.hip; off by default -- measured slower than plain launches,
-    profiles/r03_op_graph*.log).  Replays must really happen, must read the CURRENT
-    contents of the operands (only pointers and scalars are baked in), and must
-    be bit for bit the plain path -- for a single matrix, for the batched family
-    with per-slice coefficients, and in a whole solve."""
-    import heateq_mpi as hm
-    from source.linalg import PCG
-    lib = stk.lib()
-    h = hm.HeatEquationMPI(J_space=4, J_time=3)
-    n_loc, M = h.N, h.M
-    rng = np.random.RandomState(77)
-    dd = h.dofs_distr
-    xs = [_vec(dd, rng.rand(n_loc, M)) for _ in range(3)]
-    fam, (cm, kind) = h.C_family, h.C_family.slice_tables(list(h.W.levels))
-    try:
-        outs = {}
-        for graph in (0, 1):
-            stk.check(lib.stk_set_tuning(b'mg_graph', graph))
-            stk.check(lib.stk_set_tuning(b'mg_graph_replays', 0))
-            buf_in = torch.empty_like(xs[0].buf)
-            out_k, out_f = torch.empty_like(buf_in), torch.empty_like(buf_in)
-            res = []
-            for rep in range(6):  # same buffers, new contents every time
-                buf_in.copy_(xs[rep % 3].buf)
-                h.Kinv_x.apply(buf_in, out=out_k, n_loc=n_loc)
-                fam.apply(buf_in, out=out_f, n_loc=n_loc, cm=cm, kind=kind)
-                res.append((out_k.clone(), out_f.clone()))
-            outs[graph] = res
-            if graph:
-                stk.check(lib.stk_set_tuning(b'mg_graph_replays', 8))  # 2 x (6 - 2) at least
-            else:
-                assert lib.stk_set_tuning(b'mg_graph_replays', 1) != 0  # none without the key
-        for (k0, f0), (k1, f1) in zip(outs[0], outs[1]):
-            assert torch.equal(k0, k1) and torch.equal(f0, f1)
-        hists = {}
-        for graph in (0, 1):
-            stk.check(lib.stk_set_tuning(b'mg_graph', graph))
-            hist = []
-            _, it = PCG(h.WT_S_W, h.P, h.rhs, history=hist)
-            hists[graph] = (it, hist)
-        assert hists[0] == hists[1]
-    finally:
-        stk.check(lib.stk_set_tuning(b'mg_graph', 0))
-
-
 def test_strip_wise_sweeps_are_exact(stk):
     """Smoothing run strip by strip (ALL sweeps and dependency groups on one
     strip of bands before the next, every stage shifted by one band: mg.hip)
@@ -2391,8 +2343,8 @@ def test_strip_wise_sweeps_are_exact(stk):
 
 
 def test_band_merge_does_not_change_a_bit(stk):
-    """Bands of several mesh rows for the strip-wise sweeps (MultiGridFamily(band_merge),
-    tuning key mg_band_merge for the C planner): coarser bands keep "coupled
+    """Bands of several mesh rows for the strip-wise sweeps (MultiGridFamily(band_merge);
+    ADVICE r5): coarser bands keep "coupled
     rows at most one band apart", so the V-cycle is the same to the bit for merge = 1, 6
     and 64, at two slab lengths, from the Python planner and from the C planner -- and
     the fine levels still run strip by strip (launch counter) unless the merge leaves

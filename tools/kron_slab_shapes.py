@@ -22,7 +22,6 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--J_space', type=int, default=9)
 ap.add_argument('--shapes', default='65:0:0,33:0:1,32:1:0,17:1:1,16:1:1,9:1:1,8:1:1')
 ap.add_argument('--tune', default='')  # key=value,...
-ap.add_argument('--flags', default='0,1,2,3')  # pack_flags values to time
 args = ap.parse_args()
 for kv in filter(None, args.tune.split(',')):
     k, v = kv.split('=')
@@ -70,18 +69,15 @@ for shape in args.shapes.split(','):
             _lib.stream(), M, _lib.ptr(g[0] if lo else None), _lib.ptr(g[1] if hi else None), _lib.ptr(gh)))
     y2 = torch.empty_like(x)
     pspecs = [(tri[0], 0), (tri[1], 1)]
-    for flags in [int(v) for v in args.flags.split(',')]:
-        _lib.check(_lib.lib().stk_set_tuning(b'pack_flags', flags))
-        one = ell.packed_variant(1)
-        ms1 = timed(lambda: one.apply(pspecs, x, gh, n_loc, ld, 0.0, y2))
-        msp = timed(lambda: ell.packed.apply(pspecs, x, gh, n_loc, ld, 0.0, y2))
-        ell.apply(specs, n_loc, ld, 0.0, y)
-        err = float((y2 - y).abs().max())
-        print('                     packed, one row per slot row: %.3f ms' % ms1)
-        print('                     packed flags=%d: %.3f ms  %.0f GB/s algorithmic (%.1f%% of 8 TB/s)  max|diff to plain| %.1e  -> x%d ranks: %.2f TB/s aggregate'
-              % (flags, msp, nbytes / msp / 1e6, nbytes / msp / 1e6 / 80, err, round(65 / n_loc),
-                 round(65 / n_loc) * nbytes / msp / 1e9))
-    _lib.check(_lib.lib().stk_set_tuning(b'pack_flags', 3))
+    one = ell.packed_variant(1)
+    ms1 = timed(lambda: one.apply(pspecs, x, gh, n_loc, ld, 0.0, y2))
+    msp = timed(lambda: ell.packed.apply(pspecs, x, gh, n_loc, ld, 0.0, y2))
+    ell.apply(specs, n_loc, ld, 0.0, y)
+    err = float((y2 - y).abs().max())
+    print('                     packed, one row per slot row: %.3f ms' % ms1)
+    print('                     packed: %.3f ms  %.0f GB/s algorithmic (%.1f%% of 8 TB/s)  max|diff to plain| %.1e  -> x%d ranks: %.2f TB/s aggregate'
+          % (msp, nbytes / msp / 1e6, nbytes / msp / 1e6 / 80, err, round(65 / n_loc),
+             round(65 / n_loc) * nbytes / msp / 1e9))
     if lo or hi:
         # the WHOLE step of a rank but for the wire time: what the exchange sends is
         # packed out of the slab (stk_halo_pack) and what arrives enters the apply
@@ -138,4 +134,3 @@ for shape in args.shapes.split(','):
               'pack + pass without ghosts (%.3f, runs beside the exchange) + ghost share (%.3f) = %.3f ms, of which %.3f ms '
               'after the halo has arrived  (rel. diff to plain %.1e)' % (ms_pack, ms_a, ms_main, ms_go, ms_b,
                                                                         ms_go, err))
-    _lib.check(_lib.lib().stk_set_tuning(b'pack_flags', 3))

@@ -20,10 +20,7 @@ ap.add_argument('--J_time', type=int, default=6)
 ap.add_argument('--J_space', type=int, default=9)
 ap.add_argument('--iters', type=int, default=5)
 ap.add_argument('--problem', default='square')
-ap.add_argument('--alternate', type=int, default=1)
 ap.add_argument('--fuse', type=int, default=1)
-ap.add_argument('--coarse-rows', type=int, default=4096)
-ap.add_argument('--coarse-pairs', type=int, default=0)
 ap.add_argument('--fuse-restrict', type=int, default=1)
 ap.add_argument('--zero-start', type=int, default=1)
 ap.add_argument('--arithmetic', default='accurate', help="HeatEquationMPI's arithmetic mode (accurate = the default, fast, reference)")
@@ -32,10 +29,7 @@ ap.add_argument('--only', default='', help='comma-separated subset of the rows (
 ap.add_argument('--wavelettransform', default=None, help="HeatEquationMPI's wavelet mode (composite, original, interleaved)")
 args = ap.parse_args()
 from source import _lib  # noqa: E402
-_lib.check(_lib.lib().stk_set_tuning(b'rows_alternate', args.alternate))
 _lib.check(_lib.lib().stk_set_tuning(b'mg_fuse_coarse', args.fuse))
-_lib.check(_lib.lib().stk_set_tuning(b'mg_coarse_max_rows', args.coarse_rows))
-_lib.check(_lib.lib().stk_set_tuning(b'mg_coarse_pairs', args.coarse_pairs))
 _lib.check(_lib.lib().stk_set_tuning(b'mg_fuse_restrict', args.fuse_restrict))
 _lib.check(_lib.lib().stk_set_tuning(b'mg_zero_start', args.zero_start))
 for kv in filter(None, args.tune.split(',')):
