@@ -287,7 +287,8 @@ int stk_partition(int32_t N, int32_t size, int32_t rank, int32_t *t_begin,
  * `allreduce` sums host doubles over the ranks (NULL on one rank).  `w` holds
  * the initial guess on entry.  `work`: stk_pcg_work_size(n) device doubles.
  * history (host, kmax entries or NULL) receives r.Pr after the initial
- * residual and after every iteration; *iters the iteration count. */
+ * residual and after every iteration; *iters the iteration count.  kmax < 1 is
+ * refused (there would be no room for the initial r.Pr). */
 typedef int (*stk_operator_fn)(void *ctx, void *stream, const double *x,
                                double *y);
 typedef int (*stk_allreduce_fn)(void *ctx, double *values, int32_t n);

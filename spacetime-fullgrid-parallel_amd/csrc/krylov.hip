@@ -87,8 +87,9 @@ int global_dot(void *stream, int64_t n, const dot_shape &s, const double *x, con
 
 int check_slab_shape(const char *who, int32_t M, int32_t n_loc, int32_t ld, int32_t N, int32_t t_begin)
 {
-    STK_REQUIRE(M > 0 && n_loc > 0 && ld >= n_loc && (ld & 1) == 0, "%s: bad slab M=%d n_loc=%d ld=%d (ld must be even)",
-                who, M, n_loc, ld);
+    STK_REQUIRE(M > 0 && n_loc > 0, "%s: bad slab M=%d n_loc=%d (both must be positive)", who, M, n_loc);
+    STK_REQUIRE(ld >= n_loc, "%s: bad slab: ld=%d is smaller than n_loc=%d", who, ld, n_loc);
+    STK_REQUIRE((ld & 1) == 0, "%s: bad slab: ld=%d must be even", who, ld);
     STK_REQUIRE(t_begin >= 0 && t_begin + n_loc <= N, "%s: time steps [%d, %d) of %d", who, t_begin, t_begin + n_loc, N);
     return 0;
 }
@@ -99,6 +100,7 @@ int pcg_core(void *stream, int64_t n, const dot_shape &shape, stk_operator_fn T,
 {
     STK_REQUIRE(n > 0 && (n & 1) == 0, "stk_pcg_solve: n=%lld must be positive and even", (long long)n);
     STK_REQUIRE(T && P && b && w && work && iters, "stk_pcg_solve: null argument");
+    STK_REQUIRE(kmax >= 1, "stk_pcg_solve: kmax=%d must be at least 1 (history holds kmax entries)", kmax);
     double *r = work, *p = work + n, *q = work + 2 * n, *z = work + 3 * n;
     double *dot_work = work + 4 * n;
     *iters = 0;

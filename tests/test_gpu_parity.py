@@ -1951,8 +1951,15 @@ def test_kron_pack_inputs_per_term(stk):
                     finally:
                         _lib.check(_lib.lib().stk_set_tuning(b'pack_multi_lanes', 1))
                     form.apply_multi(specs_, n_loc, ld, beta, y_auto)
+                    # the entry point without stated steps, called by its own name
+                    y_direct = slab(y0)
+                    _lib.check(_lib.lib().stk_kron_pack_apply_multi(
+                        _lib.stream(), ctypes.byref(form.pattern), n_loc, ld, nt,
+                        form._terms([(dev_tri[k], which[k]) for k in range(nt)]),
+                        (ctypes.c_void_p * nt)(*[_lib.ptr(x) for x in xs]), beta, _lib.ptr(y_direct)))
                     assert torch.equal(y_steps, y), tag
                     assert torch.equal(y_auto, y), tag
+                    assert torch.equal(y_direct, y), tag
                     assert torch.equal(y_turns, y), tag
                     assert relerr(y[:, :n_loc].cpu().numpy(), want) < 1e-13, tag
                     if shape == 'schur':

@@ -36,6 +36,35 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().stk_last_error() is not None
 
 
+# Declared functions that no test, product path or bench calls by name.  Keep it empty:
+# an export nobody calls is a promise nobody checks.
+UNCALLED_EXPORTS = set()
+
+
+def test_every_declared_function_is_called_somewhere():
+    """Every function of include/stk.h is called by name -- `stk_x(` -- in the suite
+    (Python and the C hosts under tests/), in the package's Python outside _lib.py's
+    prototype table, or in bench.py: the next export that nothing exercises fails
+    here instead of waiting for a review."""
+    header = open(os.path.join(REPO, 'include', 'stk.h')).read()
+    declared = set(re.findall(r'\b(stk_[a-z0-9_]+)\s*\(', header)) - {'stk_mg'}
+    texts = [open(os.path.join(REPO, 'bench.py')).read()]
+    for top in ('tests', 'spacetime-fullgrid-parallel_amd'):
+        for dirpath, _, files in os.walk(os.path.join(REPO, top)):
+            for f in files:
+                if not f.endswith(('.py', '.c', '.cpp')):
+                    continue
+                text = open(os.path.join(dirpath, f)).read()
+                if f == '_lib.py':
+                    text, n = re.subn(r'\n_PROTOTYPES = \{\n.*?\n\}\n', '\n', text, flags=re.S)
+                    assert n == 1, 'the prototype table of _lib.py was not found'
+                texts.append(text)
+    called = set(re.findall(r'\b(stk_[a-z0-9_]+)\s*\(', '\n'.join(texts)))
+    assert not UNCALLED_EXPORTS, 'keep the allow-list empty: call %s' % sorted(UNCALLED_EXPORTS)
+    missing = sorted(declared - called - UNCALLED_EXPORTS)
+    assert not missing, 'declared in stk.h, called nowhere: %s' % missing
+
+
 def test_tuning_keys_are_the_documented_ones():
     """stk_set_tuning accepts every key stk.h documents at its default value, and
     refuses, naming the key, a value outside a key's range and every key that was
