@@ -36,8 +36,6 @@
 extern "C" {
 #endif
 
-#define STK_MAX_TERMS 4
-
 /* ---- library ------------------------------------------------------------ */
 const char *stk_last_error(void);
 int stk_version(void);
@@ -48,9 +46,6 @@ int stk_device_info(int32_t *n_cu, int32_t *wave_size, int64_t *hbm_bytes);
  * range.  Launch keys act on the next launch; plan keys are read when a plan is
  * created and hold for its lifetime.  "Bit-identical" means results never depend
  * on the key; "rounding" means the last bits may change.
- *   kron_block           (launch, 0..1024, default 0) threads per workgroup of
- *                        stk_kron_sum_apply: 256, 512 or 1024; any other value
- *                        chooses by lane use.  Bit-identical.
  *   ell_wg_per_cu        (launch, 0..16, default 0) persistent workgroups per CU
  *                        of stk_kron_ell_apply; 0 = 2 for K >= 12, else 3.
  *                        Bit-identical.
@@ -358,32 +353,15 @@ int stk_lanczos_slab(void *stream, int32_t M, int32_t n_loc, int32_t ld, int32_t
  * Replaces TridiagKronMatMPI._matvec (mpi_kron.py:214-219), i.e.
  * TridiagKronIdentityMPI (:186-201) followed by IdentityKronMatMPI (:143-150),
  * and the accumulation loop of SumMPI._matvec (:77-90), in one pass.
- * All X_k share one CSR pattern (indptr/indices); vals differ per term. */
-typedef struct {
-    /* 3*n_loc coefficients [sub | diag | super]: output time row t takes
-     * sub[t]*z[t-1] + diag[t]*z[t] + super[t]*z[t+1].  NULL = identity. */
-    const double *tri;
-    const double *vals; /* nnz values of X_k on the shared pattern */
-    const double *x;    /* input vector, M x ld */
-    const double *x_lo; /* ghost time row t = -1 (length M) or NULL */
-    const double *x_hi; /* ghost time row t = n_loc (length M) or NULL */
-} stk_kron_term;
-
-/* CSR row `pos` produces output row row_ids[pos] (row_ids == NULL: pos itself).
- * The host lists the rows in the order it wants them processed (a mesh-tile or
- * RCM order keeps the gathers of one XCD inside its L2); the result does not
- * depend on that order.  Requires ld even and 16-byte aligned x, y. */
-int stk_kron_sum_apply(void *stream, int32_t M, int32_t n_loc, int32_t ld,
-                       const int32_t *indptr, const int32_t *indices,
-                       const int32_t *row_ids, int32_t n_terms,
-                       const stk_kron_term *terms_host, double beta,
-                       double *y);
-
-/* The same operator on a sliced-ELL copy of the pattern, the fast path.
- * Every row owns K slots (K <= 16): ell_idx[pos*K + e] / ell_vals[pos*K + e];
- * unused slots hold the row's own column and the value 0.  Rows are listed in
- * processing order, row pos writes output row row_ids[pos].  Entries beyond K
- * of longer rows are kept in an overflow CSR indexed by pos (NULL if none). */
+ * All X_k share one sparsity pattern; their values differ per term.
+ *
+ * Sliced-ELL form.  Every row owns K slots (K <= 16): ell_idx[pos*K + e] /
+ * ell_vals[pos*K + e]; unused slots hold the row's own column and the value 0.
+ * Rows are listed in processing order (a mesh-tile or RCM order keeps the
+ * gathers of one XCD inside its L2; the result does not depend on it), row pos
+ * writes output row row_ids[pos] (row_ids == NULL: pos itself).  Entries
+ * beyond K of longer rows are kept in an overflow CSR indexed by pos (NULL if
+ * none).  Requires ld even and 16-byte aligned x, y. */
 typedef struct {
     int32_t M, K;
     const int32_t *ell_idx;     /* M*K */
@@ -393,10 +371,14 @@ typedef struct {
 } stk_ell_pattern;
 
 typedef struct {
-    const double *tri;      /* as in stk_kron_term */
+    /* 3*n_loc coefficients [sub | diag | super]: output time row t takes
+     * sub[t]*z[t-1] + diag[t]*z[t] + super[t]*z[t+1].  NULL = identity. */
+    const double *tri;
     const double *ell_vals; /* M*K values of X_k */
     const double *ovf_vals; /* overflow values or NULL */
-    const double *x, *x_lo, *x_hi;
+    const double *x;        /* input vector, M x ld */
+    const double *x_lo;     /* ghost time row t = -1 (length M) or NULL */
+    const double *x_hi;     /* ghost time row t = n_loc (length M) or NULL */
 } stk_kron_ell_term;
 
 /* Tuning key "ell_wg_per_cu" (stk_set_tuning).  K must be one of 5, 7, 9, 12,
@@ -473,7 +455,7 @@ typedef struct {
  * order, so the results are bit-identical with rows_per_unit = 1. */
 
 typedef struct {
-    const double *tri; /* as in stk_kron_term */
+    const double *tri; /* as in stk_kron_ell_term */
     int32_t mat;       /* which matrix of the pattern */
 } stk_kron_pack_term;
 

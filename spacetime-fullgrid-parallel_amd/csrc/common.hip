@@ -36,7 +36,6 @@ struct TuneKey {
 };
 
 const TuneKey k_tune_keys[] = {
-    {"kron_block", &stk_tuning::kron_block, 0, 1024, TUNE_LAUNCH},
     {"ell_wg_per_cu", &stk_tuning::ell_wg_per_cu, 0, 16, TUNE_LAUNCH},
     {"ell_force_wide", &stk_tuning::ell_force_wide, 0, 1, TUNE_LAUNCH},
     {"rows_force_wide", &stk_tuning::rows_force_wide, 0, 1, TUNE_LAUNCH},

@@ -1,7 +1,7 @@
 // Kronecker-sum apply, ELL form:  y = beta*y + sum_k (T_k kron X_k) x_k.
 //
-// Same operator as stk_kron_sum_apply (reference source/mpi_kron.py:77-90,
-// 186-201, 214-219) on a sliced-ELL copy of the shared sparsity pattern:
+// Replaces TridiagKronMatMPI / SumMPI of the reference (source/mpi_kron.py:77-90,
+// 186-201, 214-219), on a sliced-ELL copy of the shared sparsity pattern:
 // every row owns K entry slots (short rows are padded with a zero value and
 // their own column), rows are listed in the order they are processed, and
 // entries beyond K of very long rows live in an overflow CSR.
@@ -570,7 +570,7 @@ extern "C" int stk_kron_ell_apply(void *stream, const stk_ell_pattern *pat, int3
     STK_REQUIRE(n_terms >= 1 && n_terms <= 3, "stk_kron_ell_apply: n_terms=%d not in 1..3", n_terms);
     STK_REQUIRE((n_loc + 1) / 2 + 2 <= BS, "stk_kron_ell_apply: n_loc=%d too large", n_loc);
     STK_REQUIRE((int64_t)pat->M * ld * 8 < ((int64_t)1 << 36),
-                "stk_kron_ell_apply: slab of %lld bytes exceeds 64 GiB; use stk_kron_sum_apply",
+                "stk_kron_ell_apply: slab of %lld bytes exceeds 64 GiB; use stk_kron_pack_apply / stk_kron_plan_apply",
                 (long long)pat->M * ld * 8);
     STK_REQUIRE(((uintptr_t)y & 15) == 0, "stk_kron_ell_apply: y must be 16-byte aligned");
     for (int k = 0; k < n_terms; ++k) {

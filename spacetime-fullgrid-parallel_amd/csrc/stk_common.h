@@ -35,7 +35,6 @@ static inline hipStream_t stk_stream(void *s) { return (hipStream_t)s; }
 // in stk.h).  Set from any host thread; read with relaxed loads (stk_tune), the
 // plan-time keys once per plan construction.
 struct stk_tuning {
-    std::atomic<int32_t> kron_block{0};
     std::atomic<int32_t> ell_wg_per_cu{0};
     std::atomic<int32_t> ell_force_wide{0};
     std::atomic<int32_t> rows_force_wide{0};

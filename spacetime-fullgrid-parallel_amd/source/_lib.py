@@ -18,11 +18,6 @@ c_i32, c_i64, c_f64, c_p = (ctypes.c_int32, ctypes.c_int64, ctypes.c_double,
                             ctypes.c_void_p)
 
 
-class KronTerm(ctypes.Structure):
-    _fields_ = [('tri', c_p), ('vals', c_p), ('x', c_p), ('x_lo', c_p),
-                ('x_hi', c_p)]
-
-
 # callbacks of stk_pcg_solve (include/stk.h)
 OPERATOR_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                ctypes.c_void_p, ctypes.c_void_p)
@@ -154,10 +149,6 @@ _PROTOTYPES = {
     'stk_lanczos_slab': (ctypes.c_int, [
         c_p, c_i32, c_i32, c_i32, c_i32, c_i32, OPERATOR_FN, c_p, OPERATOR_FN, c_p,
         ALLREDUCE_FN, c_p, c_p, c_i32, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p
-    ]),
-    'stk_kron_sum_apply': (ctypes.c_int, [
-        c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_i32,
-        ctypes.POINTER(KronTerm), c_f64, c_p
     ]),
     'stk_kron_ell_apply': (ctypes.c_int, [
         c_p, ctypes.POINTER(EllPattern), c_i32, c_i32, c_i32,

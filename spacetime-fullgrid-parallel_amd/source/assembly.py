@@ -208,7 +208,8 @@ def tile_row_order(mesh, rows_per_tile=None):
     the whole index range; visiting rows in this order instead keeps the
     gathers of consecutive workgroups inside the same few hundred KB, i.e. in
     the L2 of the XCD that runs them.  Purely a performance hint
-    (stk_kron_sum_apply's row_ids); results do not depend on it."""
+    (the row_ids of stk_ell_pattern and stk_pack_pattern); results do not
+    depend on it."""
     return tile_order_from_coords(mesh.points[free_dofs(mesh)], rows_per_tile,
                                   small_lexsort=False)
 

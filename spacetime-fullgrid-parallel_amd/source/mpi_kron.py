@@ -5,9 +5,10 @@ source/mpi_kron.py; same class names, constructor arguments and
 What differs from the reference is where the arithmetic runs: each ``_matvec``
 enqueues hand-written HIP kernels of libstk on the slab in HBM.
 ``TridiagKronMatMPI`` with a CSR space factor is ONE kernel (time stencil and
-CSR gather fused), and ``SumMPI`` over such terms fuses up to 4 of them in one
-pass over x and y (``stk_kron_sum_apply``) instead of a temporary and a ``+=``
-per term (reference mpi_kron.py:77-90).
+sparse gather fused), and ``SumMPI`` over such terms fuses up to 3 of them in
+one pass over x and y (``stk_kron_pack_apply``, or ``stk_kron_ell_apply`` where
+no packed plan fits) instead of a temporary and a ``+=`` per term (reference
+mpi_kron.py:77-90).
 """
 import ctypes
 
@@ -17,8 +18,7 @@ import torch
 
 from . import _lib
 from .comm import MPI
-from .linop import (SpaceMatrix, SpaceOp, as_space_op, permute_rows,
-                    row_order_for, union_pattern)
+from .linop import SpaceMatrix, SpaceOp, as_space_op
 from .mpi_vector import DofDistributionMPI, KronVectorMPI
 
 
@@ -121,7 +121,7 @@ def _local_tridiag(dofs_distr, mat_time):
 class SumMPI(LinearOperatorMPI):
     """sum_k L_k (reference mpi_kron.py:71-90).  Consecutive
     TridiagKronMatMPI terms whose space factor is a plain matrix are fused
-    into one kernel launch per group of 3 (ELL kernel) or 4 (CSR kernel)."""
+    into one kernel launch per group of 3."""
     def __init__(self, dofs_distr, linops):
         assert all(isinstance(linop, LinearOperatorMPI) for linop in linops)
         self.linops = linops
@@ -449,10 +449,10 @@ class TridiagKronMatMPI(LinearOperatorMPI):
 
 
 class _FusedKronSum:
-    """y = beta*y + sum_k (T_k kron X_k) x for up to 4 TridiagKronMatMPI terms
-    with plain CSR space factors: shared pattern, one launch.  use_ell selects
-    the persistent sliced-ELL kernel (default) or the plain CSR one."""
-    use_ell = True
+    """y = beta*y + sum_k (T_k kron X_k) x for up to 3 TridiagKronMatMPI terms
+    with plain CSR space factors: shared pattern, one launch of the packed
+    kernel, or of the persistent sliced-ELL one where no packed plan fits."""
+    use_ell = True  # bench.py reads use_ell and use_pack
     use_pack = True  # packed matrix stream when the plan fits
     # Several ranks, packed form: True = the pass over the slab runs WITHOUT the
     # ghost steps while the halo exchange is in flight and a one-lane-per-row
@@ -473,11 +473,10 @@ class _FusedKronSum:
 
     @classmethod
     def max_terms(cls):
-        return 3 if cls.use_ell else 4
+        return 3
 
     def __init__(self, dofs_distr, ops):
         assert 1 <= len(ops) <= self.max_terms()
-        self.use_ell = type(self).use_ell
         self.dofs_distr = dofs_distr
         mats = [op.space_op.mat for op in ops]
         hints = [op.mat_space for op in ops]
@@ -487,25 +486,13 @@ class _FusedKronSum:
         self.needs_hi = any(t[2, -1] != 0.0 for t in tris)
         self.tri = [_lib.to_dev(t) for t in tris]
         self.n_terms = len(ops)
-        if self.use_ell:
-            from .linop import EllMatrices
-            self.ell = EllMatrices.shared(mats, hints)
-            self.row_ids = self.ell.row_ids
-        else:
-            indptr, indices, vals = union_pattern(mats)
-            order = row_order_for(hints + mats, indptr, indices)
-            indptr, indices, vals, row_ids = permute_rows(
-                indptr, indices, vals, order)
-            self.indptr = _lib.to_dev(indptr)
-            self.indices = _lib.to_dev(indices)
-            self.row_ids = None if row_ids is None else _lib.to_dev(row_ids)
-            self.vals = [_lib.to_dev(v) for v in vals]
-            self.terms = (_lib.KronTerm * len(ops))()
+        from .linop import EllMatrices
+        self.ell = EllMatrices.shared(mats, hints)
+        self.row_ids = self.ell.row_ids
 
     def apply(self, vec_in, vec_out, beta=0.0):
         time_comm = 0.0
-        packed = (self.ell.packed_for(vec_in.n_loc)
-                  if self.use_ell and type(self).use_pack else None)
+        packed = self.ell.packed_for(vec_in.n_loc) if type(self).use_pack else None
         if packed is not None and packed.ok:
             # one pass: matrix stream packed, ghost time steps handled by an extra
             # lane per row (csrc/kron_pack.hip); the halo has to be there first
@@ -532,50 +519,34 @@ class _FusedKronSum:
             packed.apply(specs, vec_in.buf, ghosts, vec_in.n_loc, vec_in.ld, beta,
                          vec_out.buf)
             return time_comm
-        if self.use_ell:
-            # the slab-local part runs while the halo exchange is in flight
-            # (the reference overlaps the interior rows, mpi_kron.py:193-196)
-            def local():
-                self.ell.apply_local(
-                    [(self.tri[k], k, vec_in.buf, None, None)
-                     for k in range(self.n_terms)], vec_in.n_loc, vec_in.ld,
-                    beta, vec_out.buf)
+        # the slab-local part runs while the halo exchange is in flight
+        # (the reference overlaps the interior rows, mpi_kron.py:193-196)
+        def local():
+            self.ell.apply_local(
+                [(self.tri[k], k, vec_in.buf, None, None)
+                 for k in range(self.n_terms)], vec_in.n_loc, vec_in.ld,
+                beta, vec_out.buf)
 
-            if self.dofs_distr.size > 1 and (self.needs_lo or self.needs_hi):
-                if beta != 0.0:
-                    # the boundary steps are rewritten after the local part, which
-                    # needs the old y they scale: the one-call form keeps a copy
-                    time_comm = vec_in.communicate_bdr()
-                    lo = vec_in.X_lo if self.needs_lo else None
-                    hi = vec_in.X_hi if self.needs_hi else None
-                    self.ell.apply([(self.tri[k], k, vec_in.buf, lo, hi)
-                                    for k in range(self.n_terms)], vec_in.n_loc,
-                                   vec_in.ld, beta, vec_out.buf)
-                    return time_comm
-                time_comm = vec_in.communicate_bdr(callback=local)
+        if self.dofs_distr.size > 1 and (self.needs_lo or self.needs_hi):
+            if beta != 0.0:
+                # the boundary steps are rewritten after the local part, which
+                # needs the old y they scale: the one-call form keeps a copy
+                time_comm = vec_in.communicate_bdr()
                 lo = vec_in.X_lo if self.needs_lo else None
                 hi = vec_in.X_hi if self.needs_hi else None
-                self.ell.apply_ghost(
-                    [(self.tri[k], k, vec_in.buf, lo, hi)
-                     for k in range(self.n_terms)], vec_in.n_loc, vec_in.ld,
-                    vec_out.buf)
-            else:
-                local()
-            return time_comm
-        if self.dofs_distr.size > 1:
-            time_comm = vec_in.communicate_bdr()
-        lo = vec_in.X_lo if self.needs_lo else None
-        hi = vec_in.X_hi if self.needs_hi else None
-        x = _lib.ptr(vec_in.buf)
-        for k in range(self.n_terms):
-            t = self.terms[k]
-            t.tri, t.vals = _lib.ptr(self.tri[k]), _lib.ptr(self.vals[k])
-            t.x, t.x_lo, t.x_hi = x, _lib.ptr(lo), _lib.ptr(hi)
-        _lib.check(_lib.lib().stk_kron_sum_apply(
-            _lib.stream(), vec_in.M, vec_in.n_loc, vec_in.ld,
-            _lib.ptr(self.indptr), _lib.ptr(self.indices),
-            _lib.ptr(self.row_ids), self.n_terms, self.terms, beta,
-            _lib.ptr(vec_out.buf)))
+                self.ell.apply([(self.tri[k], k, vec_in.buf, lo, hi)
+                                for k in range(self.n_terms)], vec_in.n_loc,
+                               vec_in.ld, beta, vec_out.buf)
+                return time_comm
+            time_comm = vec_in.communicate_bdr(callback=local)
+            lo = vec_in.X_lo if self.needs_lo else None
+            hi = vec_in.X_hi if self.needs_hi else None
+            self.ell.apply_ghost(
+                [(self.tri[k], k, vec_in.buf, lo, hi)
+                 for k in range(self.n_terms)], vec_in.n_loc, vec_in.ld,
+                vec_out.buf)
+        else:
+            local()
         return time_comm
 
     def phase_times(self, vec_in, vec_out, reps=10):
@@ -584,8 +555,7 @@ class _FusedKronSum:
         the pack of the two boundary rows, the pass over the slab without the ghost
         steps (what runs beside the exchange), the ghost steps' share afterwards, and
         the one-pass form with ghost lanes.  None without the packed path or a GPU."""
-        packed = (self.ell.packed_for(vec_in.n_loc)
-                  if self.use_ell and type(self).use_pack else None)
+        packed = self.ell.packed_for(vec_in.n_loc) if type(self).use_pack else None
         if packed is None or not packed.ok or not vec_in.buf.is_cuda:
             return None
         if self.dofs_distr.size > 1:
@@ -624,8 +594,6 @@ class _FusedKronSum:
     def kernel_name(self, n_loc):
         """Name of the kernel instantiation `apply` launches (for the bench
         line and for matching a PMC record to the build)."""
-        if not self.use_ell:
-            return 'kron_sum_kernel<%d>' % self.n_terms
         if type(self).use_pack and self.ell.packed_for(n_loc).ok:
             ghost = self.dofs_distr.size > 1 and (self.needs_lo or self.needs_hi)
             pk = self.ell.packed_for(n_loc)

@@ -442,10 +442,10 @@ def test_full_size_properties(stk):
     assert (h.S @ x).dot(x) > 0 and (h.P @ x).dot(x) > 0
 
 
-def test_abi_error_reporting(stk):
+def test_abi_refusals_are_reported(stk):
     lib = stk.lib()
-    rc = lib.stk_kron_sum_apply(None, 10, 5, 3, None, None, None, 1, None, 0.0,
-                                None)
+    rc = lib.stk_csr_spmm(None, 10, 5, 3, None, None, None, 0.0, None, None, None,
+                          1.0, 0.0, None, None)  # ld < n_loc
     assert rc != 0 and b'bad sizes' in lib.stk_last_error()
     rc = lib.stk_wavelet_apply(None, 10, 3, 4, 0, None, None)
     assert rc != 0 and b'ld' in lib.stk_last_error()
@@ -453,12 +453,12 @@ def test_abi_error_reporting(stk):
         stk.ptr(torch.zeros(3, dtype=torch.float64))  # host tensor refused
 
 
-def test_row_orders_and_formats_do_not_change_results(stk):
+def test_row_orders_and_ell_workgroups_do_not_change_results(stk):
     """Tile order (assembly hint), reverse Cuthill-McKee (anonymous matrix);
-    sliced-ELL and CSR kernels; every workgroup size: same Kronecker apply."""
+    every persistent-workgroup count of the sliced-ELL kernel: same Kronecker
+    apply."""
     import scipy.sparse as sp
     from oracle import kron as okron
-    from source import mpi_kron
     from source.assembly import space_matrices, time_matrices
     from source.mesh import construct_2d_lshape_mesh, construct_interval
     from source.mpi_kron import SumMPI, TridiagKronMatMPI
@@ -473,20 +473,16 @@ def test_row_orders_and_formats_do_not_change_results(stk):
     want = okron.sum_apply([(A_t, M_x), (M_t, A_x), (L_t, A_x)], X)
     plain = lambda m: sp.csr_matrix(m)  # drops the stk_row_order hint
     try:
-        for use_ell in (True, False):
-            mpi_kron._FusedKronSum.use_ell = use_ell
-            key = b'ell_wg_per_cu' if use_ell else b'kron_block'
-            for mk in (lambda m: m, plain):
-                for bs in ((0, 1, 3) if use_ell else (0, 256, 512, 1024)):
-                    stk.check(stk.lib().stk_set_tuning(key, bs))
-                    op = SumMPI(dd, [TridiagKronMatMPI(dd, A_t, mk(M_x)),
-                                     TridiagKronMatMPI(dd, M_t, mk(A_x)),
-                                     TridiagKronMatMPI(dd, L_t, mk(A_x))])
-                    assert (op._groups[0].row_ids is not None)
-                    assert relerr(_np(op @ x), want) < TOL
-            stk.check(stk.lib().stk_set_tuning(key, 0))
+        for mk in (lambda m: m, plain):
+            for wg in (0, 1, 3):
+                stk.check(stk.lib().stk_set_tuning(b'ell_wg_per_cu', wg))
+                op = SumMPI(dd, [TridiagKronMatMPI(dd, A_t, mk(M_x)),
+                                 TridiagKronMatMPI(dd, M_t, mk(A_x)),
+                                 TridiagKronMatMPI(dd, L_t, mk(A_x))])
+                assert (op._groups[0].row_ids is not None)
+                assert relerr(_np(op @ x), want) < TOL
     finally:
-        mpi_kron._FusedKronSum.use_ell = True
+        stk.check(stk.lib().stk_set_tuning(b'ell_wg_per_cu', 0))
     with pytest.raises(stk.StkError):
         stk.check(stk.lib().stk_set_tuning(b'nonsense', 1))
 
