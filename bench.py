@@ -13,6 +13,13 @@ PCG iterations per second of the preconditioned solve as a secondary figure.
 One "step" = one apply of that operator to a resident vector (including the
 halo exchange when the time axis is sharded over several GPUs).  The problem
 is fixed while GPUs are added (strong scaling): each rank owns one time slab.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the
+timed steps, --dump-outputs if given (its PCG outputs come from the same two
+solves a --full run times), and the result line.  Everything else the
+benchmark measures runs with --full only: the roofline block, the timed PCG
+solves in both arithmetics (pcg, pcg_fast), the per-rank breakdown of a
+multi-rank run (multi_gpu) and the CPU baseline (cpu_baseline).
 """
 import argparse
 import json
@@ -394,8 +401,13 @@ def main():
     ap.add_argument('--J_time', type=int, default=6)
     ap.add_argument('--J_space', type=int, default=9)
     ap.add_argument('--problem', default='square')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the roofline '
+                         'block, the timed PCG solves, the per-rank breakdown of several ranks '
+                         'and the CPU baseline')
     ap.add_argument('--solve-iters', type=int, default=10,
-                    help='PCG iterations to time for iters/s (0 = skip)')
+                    help='PCG iterations to time for iters/s with --full (0 = skip); a plain '
+                         'run solves only for --dump-outputs')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-seconds', type=float, default=10.0,
                     help='time budget of each leg (1 core, all cores) of the CPU baseline')
@@ -433,8 +445,8 @@ def main():
     M_x, A_x = space_matrices(mesh_space, scipy_path=True)
     N, M = A_t.shape[0], M_x.shape[0]
 
-    # The CPU baseline (rank 0 of a one-GPU run only) runs in a CHILD process, and LAST:
-    # see run_cpu_baseline below.
+    # The CPU baseline (--full, rank 0 of a one-GPU run only) runs in a CHILD process, and
+    # LAST: see run_cpu_baseline below.
     cpu = None
     if args.cpu_baseline_only:
         nb = 16 * N * M + 12 * (M_x.nnz + A_x.nnz) + 8 * (M + 1)
@@ -444,7 +456,7 @@ def main():
             rec['pcg']['cpu_model'] = rec['cpu_model']
         print(json.dumps(rec))
         return
-    if profiler_preloaded() and not args.no_cpu_baseline:
+    if args.full and profiler_preloaded() and not args.no_cpu_baseline:
         # under a profiler the program must not start other processes
         args.no_cpu_baseline = True
         print('bench.py: profiler preload detected, CPU baseline skipped', file=sys.stderr)
@@ -542,7 +554,7 @@ def main():
 
     # kernels alone (several ranks): the same applies with the halo already
     # present, so that the roofline figure of the kernel excludes the exchange
-    if size > 1:
+    if size > 1 and args.full:
         op._matvec(x, y)
         torch.cuda.synchronize()
         ev0.record()
@@ -558,7 +570,7 @@ def main():
     # the device time of the pieces around it, each timed alone (the received rows
     # are there) -- gathered on rank 0
     per_rank = None
-    if size > 1:
+    if size > 1 and args.full:
         mine = {'rank': rank, 'n_loc': n_loc, 'step_ms': dev_ms, 'kernels_with_cached_halo_ms': kernel_ms,
                 'host_wait_for_wire_ms': wire_wait[0] / args.steps * 1e3}
         mine.update(fused.phase_times(x, y) or {})
@@ -577,9 +589,10 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = total_bytes / (ms_per_step * 1e-3) / 1e9
 
-    # ---- secondary figure: PCG iterations per second --------------------------
+    # ---- secondary figure (--full): PCG iterations per second ------------------
     # in the library's default arithmetic ('accurate': every r.Pr within 1e-10 of the
-    # CPU path) and in the 'fast' one (4 % less time, entries within 4.6e-10)
+    # CPU path) and in the 'fast' one (4 % less time, entries within 4.6e-10).  A plain
+    # run with --dump-outputs runs the same solves for their outputs and reports nothing.
     def timed_solve(arithmetic):
         import heateq_mpi as hm
         from source.linalg import PCG
@@ -601,6 +614,8 @@ def main():
         if args.dump_outputs:
             dumps['pcg_%s_w' % arithmetic] = gather_sample(comm, h.dofs_distr, w, sample)
             dumps['pcg_%s_r_dot_Pr' % arithmetic] = np.asarray(hist, dtype=np.float64)
+        if not args.full:
+            return None
         # stamps[k] is taken inside iteration k+1, after its operator apply:
         # consecutive stamps are exactly one PCG iteration apart
         n_it = len(stamps) - 1
@@ -661,25 +676,22 @@ def main():
                     'breakdown_rank0_bytes': parts}}
 
     solve = solve_fast = solve_per_rank = None
-    if args.solve_iters > 0:
+    if args.solve_iters > 0 and (args.full or args.dump_outputs):
         solve = timed_solve('accurate')
-        solve_per_rank = solve.pop('per_rank', None)
         torch.cuda.empty_cache()
         solve_fast = timed_solve('fast')
-        del solve_fast['roofline']['breakdown_rank0_bytes']
-        solve_fast.pop('per_rank', None)
+        if args.full:
+            solve_per_rank = solve.pop('per_rank', None)
+            del solve_fast['roofline']['breakdown_rank0_bytes']
+            solve_fast.pop('per_rank', None)
 
     if rank != 0:
         return
     if args.dump_outputs:
         write_dumps(args.dump_outputs, dumps)
-    if args.gpus == 1 and size == 1 and not args.no_cpu_baseline:
+    if args.full and args.gpus == 1 and size == 1 and not args.no_cpu_baseline:
         torch.cuda.synchronize()
         cpu = run_cpu_baseline()
-    achieved = my_bytes / (kernel_ms * 1e-3) / 1e9
-    kernel = fused.kernel_name(n_loc)
-    pk = fused.ell.packed_for(n_loc) if getattr(fused, 'use_ell', False) and type(fused).use_pack else None
-    traffic, traffic_src = pmc_traffic(args, size, kernel, plan_sha(pk) if pk is not None and pk.ok else None)
     out = {
         'metric': 'Kronecker-matvec GB/s (algorithmic bytes; share of 8 TB/s HBM '
                   'peak in roofline.frac) + PCG iters/s, J_time=%d J_space=%d %s'
@@ -704,7 +716,13 @@ def main():
             'parallelism': 'time-slab x%d' % size,
             'algorithmic_bytes_total': total_bytes,
         },
-        'roofline': {
+    }
+    if args.full:
+        achieved = my_bytes / (kernel_ms * 1e-3) / 1e9
+        kernel = fused.kernel_name(n_loc)
+        pk = fused.ell.packed_for(n_loc) if getattr(fused, 'use_ell', False) and type(fused).use_pack else None
+        traffic, traffic_src = pmc_traffic(args, size, kernel, plan_sha(pk) if pk is not None and pk.ok else None)
+        out['roofline'] = {
             'bound': 'hbm',
             'achieved': achieved,
             'peak': HBM_PEAK_GBS,
@@ -716,11 +734,10 @@ def main():
             'bytes_per_launch': my_bytes,
             'avg_launch_ms': kernel_ms,
             'step_ms_with_halo_exchange': dev_ms,
-        },
-        'pcg': solve,
-        'pcg_fast': solve_fast,
-    }
-    if size > 1:
+        }
+        out['pcg'] = solve
+        out['pcg_fast'] = solve_fast
+    if args.full and size > 1:
         # what the wire allows: x is invalidated every step (the reference's timing
         # protocol), so each step moves one time row of 8 M bytes to and from each
         # neighbour over ONE xGMI link (7 links x ~153 GB/s bidirectional per GPU,

@@ -197,7 +197,7 @@ def test_distributed_solve_over_rccl_on_two_gpus():
 @pytest.mark.gpu
 @pytest.mark.parametrize('nproc,backend', [(1, 'nccl'), (2, 'gloo'), (4, 'gloo')])
 def test_bench_runs_as_the_driver_launches_it(nproc, backend):
-    """bench.py itself (kron steps + a short solve), launched as the driver
+    """bench.py --full itself (kron steps + a short solve), launched as the driver
     launches it: one rank on the RCCL-backed communicator, and 2 / 4 ranks sharing
     the test box's GPU over gloo (time slabs with ghost rows, halo exchange every
     step, max-over-ranks timing, one JSON line from rank 0)."""
@@ -209,7 +209,7 @@ def test_bench_runs_as_the_driver_launches_it(nproc, backend):
            '--master-port', str(_free_port()),
            os.path.join(os.path.dirname(HERE), 'bench.py'), '--gpus', str(nproc),
            '--steps', '2', '--warmup', '1', '--J_time', '4', '--J_space', '5',
-           '--solve-iters', '2', '--no-cpu-baseline',
+           '--full', '--solve-iters', '2', '--no-cpu-baseline',
            # several ranks: WITH the untimed preheat of the default flags -- its number of
            # steps (each a halo exchange) must be agreed between the ranks, not read off each
            # rank's own clock (round 6: a two-rank run at config 3 stopped there for good)
@@ -293,8 +293,46 @@ def test_bench_started_without_a_launcher_spawns_its_ranks():
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), 'bench.py'), '--gpus', '2',
            '--steps', '2', '--warmup', '1', '--J_time', '4', '--J_space', '5',
-           '--solve-iters', '2', '--no-cpu-baseline', '--preheat', '0']
+           '--full', '--solve-iters', '2', '--no-cpu-baseline', '--preheat', '0']
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     rec = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith('{')][-1])
     assert rec['n_gpus'] == 2 and rec['value'] > 0 and 'ghost' in rec['roofline']['kernel']
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('nproc', [1, 2])
+def test_plain_bench_reports_the_headline_and_dumps_what_full_dumps(nproc, tmp_path):
+    """A plain `bench.py` run prints the headline and its description only -- the
+    roofline, the timed solves, the per-rank breakdown and the CPU baseline are
+    --full's -- yet its --dump-outputs writes the same arrays, bit for bit, as a
+    --full run.  Two ranks share the box's GPU over gloo."""
+    import json
+    import numpy as np
+    env = dict(os.environ, STK_BACKEND='gloo', OMP_NUM_THREADS='1')
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
+        env.pop(k, None)
+    base = [sys.executable, os.path.join(os.path.dirname(HERE), 'bench.py'), '--gpus', str(nproc),
+            '--steps', '2', '--warmup', '1', '--J_time', '4', '--J_space', '5',
+            '--solve-iters', '2', '--preheat', '0']
+    recs = {}
+    for mode, extra in (('plain', []), ('full', ['--full', '--no-cpu-baseline'])):
+        res = subprocess.run(base + extra + ['--dump-outputs', str(tmp_path / mode)],
+                             env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+        recs[mode] = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith('{')][-1])
+    plain, full = recs['plain'], recs['full']
+    assert sorted(plain) == sorted(['metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup',
+                                    'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
+                                    'dtype', 'data', 'config'])
+    assert set(full) == set(plain) | {'roofline', 'pcg', 'pcg_fast'} | (
+        {'multi_gpu'} if nproc > 1 else set())
+    for k in ('metric', 'unit', 'n_gpus', 'steps', 'warmup', 'higher_is_better', 'dtype', 'config'):
+        assert plain[k] == full[k], k
+    assert plain['value'] > 0 and plain['ms_per_step'] > 0
+    names = sorted(os.listdir(tmp_path / 'plain'))
+    assert names == sorted(os.listdir(tmp_path / 'full')) == sorted(
+        ['kron_y.npy', 'pcg_accurate_w.npy', 'pcg_accurate_r_dot_Pr.npy',
+         'pcg_fast_w.npy', 'pcg_fast_r_dot_Pr.npy'])
+    for name in names:
+        assert np.array_equal(np.load(tmp_path / 'plain' / name), np.load(tmp_path / 'full' / name)), name
