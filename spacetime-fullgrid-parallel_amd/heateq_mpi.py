@@ -29,7 +29,7 @@ from source.linop import (CompositeLinOp, EllMatrices, InvLinOp, as_space_op,
                           time_factor_steps)
 from source.mpi_kron import (BlockDiagMPI, CompositeMPI, LinearOperatorMPI,
                              MatKronIdentityMPI, SumMPI, TridiagKronMatMPI,
-                             _local_tridiag)
+                             _FusedKronSum, _local_tridiag)
 from source.mpi_vector import DofDistributionMPI, KronVectorMPI
 from source.multigrid import MeshHierarchy, MultiGrid, MultiGridFamily
 from source.problem import problem_helper
@@ -51,11 +51,13 @@ class SchurMPI(LinearOperatorMPI):
         S x = (I kron M_x) K u1 + (I kron A_x) K u2 + (G_t kron M_x) x
                                                    one fused kernel
     This equals the five-term sum in exact arithmetic because K (a fixed number
-    of V-cycles from zero) is linear; tests bound the difference.  The two K
-    applies are independent: they run side by side on two HIP streams
-    (MultiGrid.apply_pair; two_streams = False: one after the other)."""
+    of V-cycles from zero) is linear; tests bound the difference.  u1 and u2 are
+    two-term Kronecker sums on the shared (M_x, A_x) plan (mpi_kron._FusedKronSum,
+    which owns the halo protocol: u1 fetches the neighbours' rows, u2 finds them
+    cached).  The two K applies are independent: they run side by side on two HIP
+    streams, u2 with the second (MultiGrid.apply_pair; two_streams = False: one
+    after the other)."""
     two_streams = True
-    pack_last_stage = True  # False: the last stage in the plain sliced-ELL form (kron_ell.hip)
 
     def __init__(self, dofs_distr, A_t, L_t, M_t, G_t, M_x, A_x, Kinv_x):
         super().__init__(dofs_distr)
@@ -63,19 +65,13 @@ class SchurMPI(LinearOperatorMPI):
         self._linops = None
         self.Kinv_x = as_space_op(Kinv_x)
         self.ell = EllMatrices.shared([M_x, A_x])  # matrix 0 = M_x, 1 = A_x
-        self._couples, self._steps = {}, {}
-
-        def tri(T):
-            host = _local_tridiag(dofs_distr, T)
-            dev = _lib.to_dev(host)
-            # does the factor reach the neighbour ranks' time rows at all?
-            self._couples[id(dev)] = (host[0, 0] != 0.0, host[2, -1] != 0.0)
-            self._steps[id(dev)] = time_factor_steps(host)
-            return dev
-
-        self.tA, self.tL, self.tM, self.tG = tri(A_t), tri(L_t), tri(
-            M_t), tri(G_t)
-        self.tLT = tri(L_t.T.tocsr())
+        self._u1 = _FusedKronSum.on_plan(dofs_distr, self.ell, [(A_t, 0), (L_t, 1)])
+        self._u2 = _FusedKronSum.on_plan(dofs_distr, self.ell, [(L_t.T.tocsr(), 0), (M_t, 1)])
+        g = _local_tridiag(dofs_distr, G_t)
+        self.tG = _lib.to_dev(g)
+        # does G_t reach the neighbour ranks' time rows at all?  which steps does it read?
+        self._g_couples = (g[0, 0] != 0.0, g[2, -1] != 0.0)
+        self._g_steps = time_factor_steps(g)
 
     @property
     def linops(self):
@@ -96,82 +92,39 @@ class SchurMPI(LinearOperatorMPI):
             ]
         return self._linops
 
-    def _spec(self, tri, k, vec):
-        """(tri, matrix, x, x_lo, x_hi) with the ghost rows only where the time
-        factor couples to them."""
-        lo, hi = self._couples[id(tri)]
-        return (tri, k, vec.buf, vec.X_lo if lo else None,
-                vec.X_hi if hi else None)
-
     def _matvec(self, vec_in, vec_out):
         assert (vec_in is not vec_out)
-        self.time_communication = 0
         x = vec_in.buf
         n_loc, ld = vec_in.n_loc, vec_in.ld
         u = torch.empty_like(x)
-        packed = self.ell.packed_for(n_loc)
+        self.time_communication = self._u1.apply(vec_in, u)
         pair = getattr(self.Kinv_x, 'apply_pair', None) if self.two_streams else None
-        if packed.ok:
-            # packed matrix stream, ghost time steps fused into the one pass
-            # (csrc/kron_pack.hip); the halo has to be there first
-            ghosts = None
-            first = [(self.tA, 0), (self.tL, 1)]
-            from source.mpi_kron import _FusedKronSum
-            if (self.dofs_distr.size > 1 and not vec_in.communicated_bdr
-                    and _FusedKronSum.overlap and n_loc >= _FusedKronSum.OVERLAP_FROM):
-                # the pass over the slab without the ghost steps while the halo is
-                # in flight (reference mpi_kron.py:193-200), the two boundary steps
-                # afterwards, from the compact records the pack leaves (_FusedKronSum.OVERLAP_FROM)
-                self.time_communication = vec_in.communicate_bdr(
-                    callback=lambda: packed.apply(first, x, None, n_loc, ld, 0.0, u), records=True)
-                ghosts = vec_in.ghost_interleaved()
-                packed.apply_boundary(first, vec_in.boundary_records(), ghosts, vec_in.X_lo is not None,
-                                      vec_in.X_hi is not None, n_loc, ld, u)
-            else:
-                if self.dofs_distr.size > 1:
-                    self.time_communication = vec_in.communicate_bdr()
-                    ghosts = vec_in.ghost_interleaved()
-                packed.apply(first, x, ghosts, n_loc, ld, 0.0, u)
-            if pair is not None:
-                # the second right-hand side and its K apply on the side stream,
-                # beside the first K apply
-                def second():
-                    u2 = torch.empty_like(x)
-                    packed.apply([(self.tLT, 0), (self.tM, 1)], x, ghosts, n_loc,
-                                 ld, 0.0, u2)
-                    return u2
+        if pair is not None:
+            # the second right-hand side and its K apply on the side stream,
+            # beside the first K apply
+            def second():
+                u2 = torch.empty_like(x)
+                self._u2.apply(vec_in, u2)
+                return u2
 
-                v1, v2 = pair(u, second, n_loc=n_loc, shared=(x, ghosts))
-            else:
-                v1 = self.Kinv_x.apply(u, n_loc=n_loc)
-                packed.apply([(self.tLT, 0), (self.tM, 1)], x, ghosts, n_loc, ld,
-                             0.0, u)
-                v2 = self.Kinv_x.apply(u, n_loc=n_loc)
+            v1, v2 = pair(u, second, n_loc=n_loc, shared=(x,) + self._u2.halo_buffers(vec_in))
         else:
-            first = [(self.tA, 0, x, None, None), (self.tL, 1, x, None, None)]
-            if self.dofs_distr.size > 1:
-                # slab-local part of the first launch while the halo is in flight
-                self.time_communication = vec_in.communicate_bdr(
-                    callback=lambda: self.ell.apply_local(first, n_loc, ld, 0.0, u))
-            else:
-                self.ell.apply_local(first, n_loc, ld, 0.0, u)
-            self.ell.apply_ghost([self._spec(self.tA, 0, vec_in),
-                                  self._spec(self.tL, 1, vec_in)], n_loc, ld, u)
             v1 = self.Kinv_x.apply(u, n_loc=n_loc)
-            self.ell.apply([self._spec(self.tLT, 0, vec_in),
-                            self._spec(self.tM, 1, vec_in)], n_loc, ld, 0.0, u)
+            self._u2.apply(vec_in, u)
             v2 = self.Kinv_x.apply(u, n_loc=n_loc)
-        g_lo, g_hi = self._couples[id(self.tG)]
-        if (self.pack_last_stage and packed.ok and not packed.explicit
+        packed = self.ell.packed_for(n_loc)
+        g_lo, g_hi = self._g_couples
+        if (packed.ok and not packed.explicit
                 and not ((g_lo or g_hi) and self.dofs_distr.size > 1)):
             # the three inputs through the packed slot stream, one turn per term;
             # G_t's turn only in the lanes of the time steps it multiplies
             packed.apply_multi([(None, 0, v1), (None, 1, v2), (self.tG, 0, x)],
                                n_loc, ld, 0.0, vec_out.buf,
-                               steps=[None, None, self._steps[id(self.tG)]])
+                               steps=[None, None, self._g_steps])
         else:
             self.ell.apply([(None, 0, v1, None, None), (None, 1, v2, None, None),
-                            self._spec(self.tG, 0, vec_in)], n_loc, ld, 0.0,
+                            (self.tG, 0, x, vec_in.X_lo if g_lo else None,
+                             vec_in.X_hi if g_hi else None)], n_loc, ld, 0.0,
                            vec_out.buf)
         vec_out.communicated_bdr = False
         return vec_out
@@ -436,8 +389,6 @@ class HeatEquationMPI:
         levels = (self.W.levels if hasattr(self.W, 'levels') else
                   WaveletTransformOp(self.J_time, interleaved=True).levels)
         self.P = BlockDiagMPI(dd, [self.CAC_j[j] for j in levels])
-        if precond == 'multigrid' and family != 'reference' and schur != 'reference':
-            self.P.mid_packed = (self.S.ell, 1)  # A_x in S's packed (M_x, A_x) stream
         self.WT_S_W = CompositeMPI(dd, [self.WT, self.S, self.W])
 
         # -- RHS -- (heateq_mpi.py:188-191)

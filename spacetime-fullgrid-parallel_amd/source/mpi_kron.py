@@ -152,7 +152,7 @@ class SumMPI(LinearOperatorMPI):
         vec_tmp = None
         for g in self._groups:
             if isinstance(g, _FusedKronSum):
-                self.time_communication += g.apply(vec_in, vec_out,
+                self.time_communication += g.apply(vec_in, vec_out.buf,
                                                    beta=0.0 if first else 1.0)
             else:
                 if first:
@@ -190,16 +190,6 @@ class CompositeMPI(LinearOperatorMPI):
         return vec_out
 
 
-_SIDE = []
-
-
-def _side_stream():
-    """The second HIP stream of the process (independent halves of an operator)."""
-    if not _SIDE:
-        _SIDE.append(torch.cuda.Stream())
-    return _SIDE[0]
-
-
 class BlockDiagMPI(LinearOperatorMPI):
     """y[t] = C_t x[t] for a list of space operators indexed by the GLOBAL
     time index (reference mpi_kron.py:113-132).
@@ -207,26 +197,7 @@ class BlockDiagMPI(LinearOperatorMPI):
     Equal operator objects are applied to all their time slices in one batched
     call.  When every block is ``CompositeLinOp([C, A, C])`` with the C's taken
     from one MultiGrid family (multigrid.MultiGridFamily), all slices run
-    through a single batched V-cycle with per-slice matrix coefficients.
-
-    two_streams (default False): two column ranges of the slab through C A C side
-    by side on two HIP streams, the way S runs its two independent K applies
-    (heateq_mpi.SchurMPI).  Bit-identical, and measured SLOWER for P -- 21.1 ->
-    25.9 ms on 65-step slabs, 5.5 -> 10.0 ms on 9-step slabs
-    (profiles/r03_op_times_two_streams_P_*.log): the two halves read the same
-    cache lines of every row and each streams the matrices once more.  The K
-    applies of S gain because they are whole, independent slabs."""
-    two_streams = False
-    # (EllMatrices plan, index of the middle matrix in it) or None: the caller may
-    # name the packed plan that holds the middle factor of its C A C blocks
-    # (heateq_mpi.HeatEquationMPI does: A_x is matrix 1 of the (M_x, A_x) plan)
-    # MEASURED and left off (profiles/r04_c_op_J6_J9_*.log, r04_b_launches_by_grid_J3_J9.txt):
-    # the one-term packed pass is SLOWER than the row engine's own 5-slot copy of A_x,
-    # 0.374 against 0.301 ms on 65-step slabs (row pairs: 10 gathers per two rows, half
-    # of them for columns only M_x has), 0.085 against 0.058 ms on 9-step slabs.
-    mid_packed = None
-    pack_mid = False
-
+    through a single batched V-cycle with per-slice matrix coefficients."""
     def __init__(self, dofs_distr, matrices_space):
         M = matrices_space[0].shape[0]
         for mat in matrices_space:
@@ -272,45 +243,9 @@ class BlockDiagMPI(LinearOperatorMPI):
             b[1].apply(vec_in.buf, out=vec_out.buf, n_loc=n_loc)
         elif b is not None and b[0] == 'family':
             _, fam, (cm, kind), mid = b
-            half = ((n_loc + 1) // 2 + 1) & ~1  # even: the second range starts on a 16-byte pair
-            if type(self).two_streams and n_loc >= 8 and vec_in.buf.is_cuda and hasattr(mid, 'mat'):
-                # time slices are independent: two column ranges of the slab go
-                # through C A C side by side on two HIP streams (a twin plan owns
-                # the second set of level workspaces), filling each other's launch
-                # gaps and tails like the two K applies inside S
-                x, ld = vec_in.buf, vec_in.ld
-                t1, t2 = torch.empty_like(x), torch.empty_like(x)
-                main = torch.cuda.current_stream()
-                side = _side_stream()
-                side.wait_stream(main)
-                for (off, n), stream, twin in (((0, half), main, False),
-                                               ((half, n_loc - half), side, True)):
-                    with torch.cuda.stream(stream):
-                        cols = lambda t: t[:, off:]
-                        kw = dict(n_loc=n, cm=cm[off:], kind=kind[off:], twin=twin, ld=ld)
-                        fam.apply(cols(x), out=cols(t1), **kw)
-                        mid.apply(cols(t1), out=cols(t2), n_loc=n, ld=ld)
-                        fam.apply(cols(t2), out=cols(vec_out.buf), **kw)
-                for t in (x, t1, t2, vec_out.buf):
-                    t.record_stream(side)
-                main.wait_stream(side)
-            else:
-                t1 = fam.apply(vec_in.buf, n_loc=n_loc, cm=cm, kind=kind)
-                packed = None
-                if self.mid_packed is not None and type(self).pack_mid:
-                    packed = self.mid_packed[0].packed_for(n_loc)
-                if packed is not None and packed.ok and packed.rows_per_unit == 2:
-                    # I kron A_x on the packed slot stream S and the metric's operator
-                    # share (4 bytes per slot instead of 12), where that stream serves
-                    # row PAIRS (5 gathers per row, as many as A_x's own rows have; the
-                    # one-row form gathers the union pattern's 7: 0.085 against 0.058 ms
-                    # on 9-step slabs, profiles/r04_b_launches_by_grid_J3_J9.txt)
-                    t2 = torch.empty_like(t1)
-                    packed.apply([(None, self.mid_packed[1])], t1, None, n_loc,
-                                 vec_in.ld, 0.0, t2)
-                else:
-                    t2 = mid.apply(t1, n_loc=n_loc)
-                fam.apply(t2, out=vec_out.buf, n_loc=n_loc, cm=cm, kind=kind)
+            t1 = fam.apply(vec_in.buf, n_loc=n_loc, cm=cm, kind=kind)
+            t2 = mid.apply(t1, n_loc=n_loc)
+            fam.apply(t2, out=vec_out.buf, n_loc=n_loc, cm=cm, kind=kind)
         else:
             # general case: the time slices of every distinct operator object
             # together (one slice at a time if all operators differ)
@@ -435,7 +370,7 @@ class TridiagKronMatMPI(LinearOperatorMPI):
     def _matvec(self, vec_in, vec_out):
         if self.fusable:
             assert (vec_in is not vec_out)
-            self.time_communication = self._fused.apply(vec_in, vec_out, 0.0)
+            self.time_communication = self._fused.apply(vec_in, vec_out.buf, 0.0)
         else:
             self.T_I._matvec(vec_in, vec_out)
             self.I_M._matvec(vec_out, vec_out)
@@ -449,105 +384,121 @@ class TridiagKronMatMPI(LinearOperatorMPI):
 
 
 class _FusedKronSum:
-    """y = beta*y + sum_k (T_k kron X_k) x for up to 3 TridiagKronMatMPI terms
-    with plain CSR space factors: shared pattern, one launch of the packed
-    kernel, or of the persistent sliced-ELL one where no packed plan fits."""
+    """y = beta*y + sum_k (T_k kron X_k) x for up to 3 tridiagonal time factors T_k
+    and plain CSR space factors X_k on one shared pattern (an EllMatrices plan): one
+    launch of the packed kernel (csrc/kron_pack.hip), or of the persistent sliced-ELL
+    one (csrc/kron_ell.hip) where no packed plan fits or ``use_pack`` is off.
+
+    On several ranks the first and the last local time step need a row from the
+    neighbour rank.  ``_form`` decides how, ``apply`` does it:
+
+    * overlapped: the pass over the slab WITHOUT the ghost steps runs while the halo
+      exchange is in flight (the reference overlaps the exchange with the interior
+      rows, mpi_kron.py:193-200) and the two boundary steps are recomputed afterwards
+      -- packed: from the compact records the halo pack leaves beside the rows it
+      extracts (stk_kron_pack_boundary_apply); sliced ELL: from the slab
+      (stk_kron_ell_ghost_apply);
+    * one pass: wait for the halo (or find it cached), then one launch that reads the
+      received rows (packed: as an extra lane per row).
+
+    Both forms, and the one-rank kernel, round every entry the same way: the result
+    does not depend on where the slabs are cut.  Measurements: DESIGN.md section 4."""
     use_ell = True  # bench.py reads use_ell and use_pack
     use_pack = True  # packed matrix stream when the plan fits
-    # Several ranks, packed form: True = the pass over the slab runs WITHOUT the
-    # ghost steps while the halo exchange is in flight and a one-lane-per-row
-    # kernel recomputes the first and last local step afterwards (the reference
-    # overlaps the exchange with the interior rows, mpi_kron.py:193-200); False =
-    # wait for the halo, then one pass with the ghost steps as an extra lane per
-    # row.  A halo that is already there (cached) always takes the one-pass form.
-    # Both forms, and the one-rank kernel, round every entry the same way.
-    # Round 6: the two boundary steps are RECOMPUTED (what makes the forms bit-equal).
-    # From the slab itself that gathers 16 bytes per 128-byte line and costs 0.069 / 0.130
-    # / 0.079 ms at 9 / 17 / 33 steps of 1 046 529 rows where adding a share cost 0.042 /
-    # 0.052 / 0.041 ms; from the compact records the pack kernel leaves beside the rows it
-    # extracts (stk_halo_pack_records, stk_kron_pack_boundary_apply) 0.038 / 0.038 / 0.035
-    # ms: the overlapped form wins on every slab length again
-    # (profiles/r06_slab_shapes_J9.log, _J10.log; DESIGN.md section 4).
-    overlap = True
-    OVERLAP_FROM = 1
+    overlap = True  # False: always wait for the halo, then one pass
+    OVERLAP_FROM = 1  # local time steps from which the overlapped form is taken
 
     @classmethod
     def max_terms(cls):
         return 3
 
     def __init__(self, dofs_distr, ops):
-        assert 1 <= len(ops) <= self.max_terms()
+        from .linop import EllMatrices
+        ell = EllMatrices.shared([op.space_op.mat for op in ops],
+                                 [op.mat_space for op in ops])
+        self._set(dofs_distr, ell, [(op.mat_time, k) for k, op in enumerate(ops)])
+
+    @classmethod
+    def on_plan(cls, dofs_distr, ell, terms):
+        """The sum over `terms` = [(time matrix, index of the space matrix in the
+        EllMatrices plan `ell`), ...]: for callers that hold the plan already."""
+        self = cls.__new__(cls)
+        self._set(dofs_distr, ell, terms)
+        return self
+
+    def _set(self, dofs_distr, ell, terms):
+        assert 1 <= len(terms) <= self.max_terms()
         self.dofs_distr = dofs_distr
-        mats = [op.space_op.mat for op in ops]
-        hints = [op.mat_space for op in ops]
-        self.nnz_terms = [int(m.nnz) for m in mats]
-        tris = [_local_tridiag(dofs_distr, op.mat_time) for op in ops]
+        self.ell = ell
+        self.row_ids = ell.row_ids
+        self.n_terms = len(terms)
+        self.nnz_terms = [ell.nnz_terms[k] for _, k in terms]
+        tris = [_local_tridiag(dofs_distr, mat_time) for mat_time, _ in terms]
+        # does any time factor reach the neighbour ranks' rows at all?
         self.needs_lo = any(t[0, 0] != 0.0 for t in tris)
         self.needs_hi = any(t[2, -1] != 0.0 for t in tris)
         self.tri = [_lib.to_dev(t) for t in tris]
-        self.n_terms = len(ops)
-        from .linop import EllMatrices
-        self.ell = EllMatrices.shared(mats, hints)
-        self.row_ids = self.ell.row_ids
+        self._specs = [(tri, k) for tri, (_, k) in zip(self.tri, terms)]
 
-    def apply(self, vec_in, vec_out, beta=0.0):
-        time_comm = 0.0
-        packed = self.ell.packed_for(vec_in.n_loc) if type(self).use_pack else None
-        if packed is not None and packed.ok:
-            # one pass: matrix stream packed, ghost time steps handled by an extra
-            # lane per row (csrc/kron_pack.hip); the halo has to be there first
-            ghosts = None
-            specs = [(self.tri[k], k) for k in range(self.n_terms)]
-            halo = self.dofs_distr.size > 1 and (self.needs_lo or self.needs_hi)
-            if (halo and type(self).overlap and not vec_in.communicated_bdr
-                    and beta == 0.0 and vec_in.n_loc >= type(self).OVERLAP_FROM):
-                # (the boundary steps are REWRITTEN afterwards: a beta != 0 would
-                # need the old values the pass has replaced -- one-pass form then)
+    def _packed(self, n_loc):
+        """The packed form of the plan for slabs of n_loc steps, None: sliced ELL."""
+        packed = self.ell.packed_for(n_loc) if type(self).use_pack else None
+        return packed if packed is not None and packed.ok else None
+
+    def _form(self, n_loc, halo_cached=False, beta=0.0):
+        """How one apply gets its neighbours' rows: None (one rank, or no term
+        couples to a neighbour), 'overlapped' or 'one pass'.  The overlapped form
+        REWRITES the boundary steps after the pass, so a beta != 0 -- which needs the
+        old y there -- and a halo that is already there take one pass."""
+        if self.dofs_distr.size == 1 or not (self.needs_lo or self.needs_hi):
+            return None
+        cls = type(self)
+        if cls.overlap and not halo_cached and beta == 0.0 and n_loc >= cls.OVERLAP_FROM:
+            return 'overlapped'
+        return 'one pass'
+
+    def apply(self, vec_in, out, beta=0.0):
+        """out = beta*out + (sum of the terms) vec_in for a slab tensor `out`;
+        returns the host's wait for the halo in seconds."""
+        x, n_loc, ld = vec_in.buf, vec_in.n_loc, vec_in.ld
+        form = self._form(n_loc, vec_in.communicated_bdr, beta)
+        packed = self._packed(n_loc)
+        if packed is not None:
+            specs = self._specs
+            if form == 'overlapped':
                 time_comm = vec_in.communicate_bdr(callback=lambda: packed.apply(
-                    specs, vec_in.buf, None, vec_in.n_loc, vec_in.ld, 0.0,
-                    vec_out.buf), records=True)
-                # the two boundary steps from the compact records the pack left and the
-                # interleaved received rows: both sides in one lane per slot row
+                    specs, x, None, n_loc, ld, 0.0, out), records=True)
+                # both sides in one lane per slot row, from the records and the
+                # interleaved received rows
                 packed.apply_boundary(specs, vec_in.boundary_records(), vec_in.ghost_interleaved(),
                                       self.needs_lo and vec_in.X_lo is not None,
-                                      self.needs_hi and vec_in.X_hi is not None,
-                                      vec_in.n_loc, vec_in.ld, vec_out.buf)
+                                      self.needs_hi and vec_in.X_hi is not None, n_loc, ld, out)
                 return time_comm
-            if halo:
-                time_comm = vec_in.communicate_bdr()
-                ghosts = vec_in.ghost_interleaved()
-            packed.apply(specs, vec_in.buf, ghosts, vec_in.n_loc, vec_in.ld, beta,
-                         vec_out.buf)
+            time_comm = vec_in.communicate_bdr() if form else 0.0
+            packed.apply(specs, x, vec_in.ghost_interleaved() if form else None, n_loc, ld, beta, out)
             return time_comm
-        # the slab-local part runs while the halo exchange is in flight
-        # (the reference overlaps the interior rows, mpi_kron.py:193-196)
-        def local():
-            self.ell.apply_local(
-                [(self.tri[k], k, vec_in.buf, None, None)
-                 for k in range(self.n_terms)], vec_in.n_loc, vec_in.ld,
-                beta, vec_out.buf)
 
-        if self.dofs_distr.size > 1 and (self.needs_lo or self.needs_hi):
-            if beta != 0.0:
-                # the boundary steps are rewritten after the local part, which
-                # needs the old y they scale: the one-call form keeps a copy
-                time_comm = vec_in.communicate_bdr()
-                lo = vec_in.X_lo if self.needs_lo else None
-                hi = vec_in.X_hi if self.needs_hi else None
-                self.ell.apply([(self.tri[k], k, vec_in.buf, lo, hi)
-                                for k in range(self.n_terms)], vec_in.n_loc,
-                               vec_in.ld, beta, vec_out.buf)
-                return time_comm
-            time_comm = vec_in.communicate_bdr(callback=local)
-            lo = vec_in.X_lo if self.needs_lo else None
-            hi = vec_in.X_hi if self.needs_hi else None
-            self.ell.apply_ghost(
-                [(self.tri[k], k, vec_in.buf, lo, hi)
-                 for k in range(self.n_terms)], vec_in.n_loc, vec_in.ld,
-                vec_out.buf)
-        else:
-            local()
+        def specs(ghosts):
+            lo = vec_in.X_lo if ghosts and self.needs_lo else None
+            hi = vec_in.X_hi if ghosts and self.needs_hi else None
+            return [(tri, k, x, lo, hi) for tri, k in self._specs]
+
+        if form == 'overlapped':
+            time_comm = vec_in.communicate_bdr(
+                callback=lambda: self.ell.apply_local(specs(False), n_loc, ld, 0.0, out))
+            self.ell.apply_ghost(specs(True), n_loc, ld, out)
+            return time_comm
+        time_comm = vec_in.communicate_bdr() if form else 0.0
+        self.ell.apply(specs(bool(form)), n_loc, ld, beta, out)
         return time_comm
+
+    def halo_buffers(self, vec_in):
+        """The received rows an apply on the cached halo of `vec_in` reads besides the
+        slab, as a tuple of tensors: for a caller that runs it on another stream."""
+        if self._form(vec_in.n_loc, True) is None:
+            return ()
+        return (vec_in.ghost_interleaved() if self._packed(vec_in.n_loc) is not None
+                else vec_in.ghost_pair(),)
 
     def phase_times(self, vec_in, vec_out, reps=10):
         """Device milliseconds of the pieces of one multi-rank apply on the packed
@@ -555,13 +506,13 @@ class _FusedKronSum:
         the pack of the two boundary rows, the pass over the slab without the ghost
         steps (what runs beside the exchange), the ghost steps' share afterwards, and
         the one-pass form with ghost lanes.  None without the packed path or a GPU."""
-        packed = self.ell.packed_for(vec_in.n_loc) if type(self).use_pack else None
-        if packed is None or not packed.ok or not vec_in.buf.is_cuda:
+        packed = self._packed(vec_in.n_loc)
+        if packed is None or not vec_in.buf.is_cuda:
             return None
         if self.dofs_distr.size > 1:
             vec_in.communicate_bdr()
         n_loc, ld, M = vec_in.n_loc, vec_in.ld, vec_in.M
-        specs = [(self.tri[k], k) for k in range(self.n_terms)]
+        specs = self._specs
         lo = vec_in.X_lo if self.needs_lo else None
         hi = vec_in.X_hi if self.needs_hi else None
         send = torch.empty((2, M), dtype=torch.float64, device=vec_in.buf.device)
@@ -594,14 +545,13 @@ class _FusedKronSum:
     def kernel_name(self, n_loc):
         """Name of the kernel instantiation `apply` launches (for the bench
         line and for matching a PMC record to the build)."""
-        if type(self).use_pack and self.ell.packed_for(n_loc).ok:
-            ghost = self.dofs_distr.size > 1 and (self.needs_lo or self.needs_hi)
-            pk = self.ell.packed_for(n_loc)
-            overlapped = ghost and type(self).overlap and n_loc >= type(self).OVERLAP_FROM
+        pk = self._packed(n_loc)
+        if pk is not None:
+            form = self._form(n_loc)
             return 'kron_pack_kernel<%d, %d, %s, %s%s>' % (
                 self.n_terms, pk.K,
-                'pass without ghost steps beside the exchange + boundary kernel' if overlapped
-                else 'ghost lanes' if ghost else 'no ghosts',
+                {'overlapped': 'pass without ghost steps beside the exchange + boundary kernel',
+                 'one pass': 'ghost lanes', None: 'no ghosts'}[form],
                 'row pairs' if pk.rows_per_unit == 2 else 'single rows',
                 ', explicit values' if pk.explicit else '')
         return 'kron_ell_kernel<%d, shared input, %d>' % (self.n_terms, self.ell.K)

@@ -742,10 +742,8 @@ class _DeviceHierarchy:
             if handle is not None:
                 _lib.check(_lib.lib().stk_mg_set_option(handle, key.encode(), int(value)))
 
-    def apply(self, x, out, n_loc, ca, cm, kind, twin=False, ld=None):
-        """`ld`: leading dimension when x / out are column ranges of wider slabs
-        (their data pointers then start inside a row)."""
-        ld = x.shape[1] if ld is None else ld
+    def apply(self, x, out, n_loc, ca, cm, kind, twin=False):
+        ld = x.shape[1]
         n_loc = ld if n_loc is None else n_loc
         if out is None:
             out = torch.empty_like(x)
@@ -980,8 +978,8 @@ class MultiGridFamily:
         kind = _lib.to_dev(np.array([k + 1 for k in members], dtype=np.int32))
         return cm, kind
 
-    def apply(self, x, out=None, n_loc=None, cm=None, kind=None, twin=False, ld=None):
-        return self._dev.apply(x, out, n_loc, self.ca, cm, kind, twin=twin, ld=ld)
+    def apply(self, x, out=None, n_loc=None, cm=None, kind=None):
+        return self._dev.apply(x, out, n_loc, self.ca, cm, kind)
 
     def apply_member(self, k, x, out=None, n_loc=None):
         n = x.shape[1] if n_loc is None else n_loc

@@ -102,22 +102,29 @@ def main():
         assert its3 == it_o, (its3, it_o)
         assert np.allclose(hist3, hist_o, rtol=1e-10, atol=1e-30)
         assert rel(got3, wo) < 1e-9
-    # both forms of the halo on the packed path give the same operator
-    # (the overlapped form is the default from 24 steps on: taken here on every slab)
+    # every form of the halo protocol gives the same operator, bit for bit: the packed
+    # stream and the sliced-ELL fallback (use_pack), each with the pass beside the exchange
+    # (taken here on every slab: OVERLAP_FROM = 1) and with one pass after it -- for the
+    # metric operator and for S, whose first two stages are two such sums
     from source.mpi_kron import _FusedKronSum
     default_from = _FusedKronSum.OVERLAP_FROM
     _FusedKronSum.OVERLAP_FROM = 1
+    forms = {}
     try:
-        x._invalidate()
-        y_overlap = gathered(metric @ x)
-        _FusedKronSum.overlap = False
-        x._invalidate()
-        y_one_pass = gathered(metric @ x)
+        for use_pack in (True, False):
+            for overlap in (True, False):
+                _FusedKronSum.use_pack, _FusedKronSum.overlap = use_pack, overlap
+                for name, op in (('metric', metric), ('S', h.S)):
+                    x._invalidate()
+                    forms[name, use_pack, overlap] = gathered(op @ x)
     finally:
-        _FusedKronSum.overlap = True
+        _FusedKronSum.use_pack = _FusedKronSum.overlap = True
         _FusedKronSum.OVERLAP_FROM = default_from
     if rank == 0:
-        assert np.array_equal(y_overlap, y_one_pass) and rel(y_overlap, want_metric) < 1e-12
+        for (name, use_pack, overlap), y in forms.items():
+            assert np.array_equal(y, forms[name, True, True]), (name, use_pack, overlap)
+        assert rel(forms['metric', True, True], want_metric) < 1e-12
+        assert rel(forms['S', True, True], o.S(X)) < 1e-11
     # the mirrored driver end to end on the same ranks (reference heateq_mpi.py:205-312):
     # its first-contact record -- start-up line per rank, on 3 ranks and more the probe
     # that chooses the halo form -- and the same solve

@@ -2272,9 +2272,14 @@ def test_two_stream_multigrid_pair_is_exact(stk):
     the two V-cycle chains side by side on two HIP streams (twin plan = second set
     of level workspaces).  Results must be bit for bit those of two applies on one
     stream, buffers must survive the caching allocator across streams (repeated
-    with fresh allocations), and S itself must not depend on the switch.  P does
-    the same with two column ranges of the slab (time slices are independent):
-    BlockDiagMPI.two_streams."""
+    with fresh allocations), and S itself must not depend on the switch.
+
+    The library also takes a COLUMN RANGE of a wider slab (stk_mg_apply,
+    stk_ell_spmm: pointer inside a row, ld of the whole slab, the per-slice cm /
+    kind tables offset alike): two ranges through C A C, called through the C ABI on
+    the family's plan and A_x's row-engine copy, give P of the whole slab bit for
+    bit -- also with mg_zero_start = 0, whose level-wide memset must stay inside the
+    columns of its own range."""
     import heateq_mpi as hm
     h = hm.HeatEquationMPI(J_space=5, J_time=4)
     K = h.Kinv_x
@@ -2290,26 +2295,46 @@ def test_two_stream_multigrid_pair_is_exact(stk):
         del a, b, got  # released while the side stream may still hold them
         junk = [torch.rand((M, n_loc + (n_loc & 1)), dtype=torch.float64, device='cuda') for _ in range(3)]
         del junk
-    from source.mpi_kron import BlockDiagMPI
-    for J_time in (4, 3, 5):  # 17, 9 and 33 time steps: odd slabs, uneven halves
+    lib = stk.lib()
+
+    def cac_by_column_ranges(hh, x):
+        _, fam, (cm, kind), mid = hh.P._batched
+        n_loc, ld = x.n_loc, x.ld
+        plan, rows = fam._dev.ensure_plan(ld), mid._ell_form()
+        half = ((n_loc + 1) // 2 + 1) & ~1  # even: the second range starts on a 16-byte pair
+        t1, t2 = torch.empty_like(x.buf), torch.empty_like(x.buf)
+        out = x._like()
+        out.buf.fill_(float('nan'))  # a column that no range wrote must not pass by luck
+        at = lambda t, off: stk.ptr(t) + t.element_size() * off
+        for off, n in ((0, half), (half, n_loc - half)):
+            def family(src, dst):
+                stk.check(lib.stk_mg_apply(plan, stk.stream(), n, ld, fam.ca, at(cm, off), at(kind, off),
+                                           at(src, off), at(dst, off)))
+
+            family(x.buf, t1)
+            stk.check(lib.stk_ell_spmm(stk.stream(), ctypes.byref(rows.struct), n, ld, hh.M, 1.0, None,
+                                       at(t1, off), 1.0, 0.0, None, at(t2, off)))
+            family(t2, out.buf)
+        return _np(out)
+
+    for J_time in (4, 3, 5):  # 17, 9 and 33 time steps: odd slabs, uneven ranges
         hh = h if J_time == 4 else hm.HeatEquationMPI(J_space=4, J_time=J_time)
         x = _vec(hh.dofs_distr, rng.rand(hh.N, hh.M))
-        BlockDiagMPI.two_streams = True  # (off by default: measured slower for P)
         try:
-            y_two, p_two = _np(hh.S @ x), _np(hh.P @ x)
-            # zero-start off: the level-wide memset of the first sweep must stay
-            # inside the columns of its own half
-            stk.check(stk.lib().stk_set_tuning(b'mg_zero_start', 0))
-            p_two_memset = _np(hh.P @ x)
-            stk.check(stk.lib().stk_set_tuning(b'mg_zero_start', 1))
-            hm.SchurMPI.two_streams = BlockDiagMPI.two_streams = False
+            y_two, p_whole = _np(hh.S @ x), _np(hh.P @ x)
+            p_ranges = cac_by_column_ranges(hh, x)
+            stk.check(lib.stk_set_tuning(b'mg_zero_start', 0))
+            p_ranges_memset = cac_by_column_ranges(hh, x)
+            stk.check(lib.stk_set_tuning(b'mg_zero_start', 1))
+            hm.SchurMPI.two_streams = False
             x._invalidate()
-            y_one, p_one = _np(hh.S @ x), _np(hh.P @ x)
+            y_one = _np(hh.S @ x)
         finally:
-            hm.SchurMPI.two_streams, BlockDiagMPI.two_streams = True, False
-            stk.check(stk.lib().stk_set_tuning(b'mg_zero_start', 1))
-        assert np.array_equal(y_two, y_one) and np.array_equal(p_two, p_one), J_time
-        assert np.array_equal(p_two_memset, p_one), J_time
+            hm.SchurMPI.two_streams = True
+            stk.check(lib.stk_set_tuning(b'mg_zero_start', 1))
+        assert np.array_equal(y_two, y_one), J_time
+        assert np.array_equal(p_ranges, p_whole), J_time
+        assert np.array_equal(p_ranges_memset, p_whole), J_time
 
 
 def test_strip_wise_sweeps_are_exact(stk):
