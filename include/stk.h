@@ -715,6 +715,90 @@ int stk_time_dense_apply(void *stream, int32_t M, int32_t n_in, int32_t ld_in,
                          int32_t n_out, int32_t ld_out, const double *T,
                          const double *x, double *y);
 
+/* ---- test-space slabs: the time side of B, B^T and K on Y ---------------------
+ * The test space of the serial driver is discontinuous P1 in time (heateq.py:37-51):
+ * two dofs per time element, 2e + a.  Its time factors are rectangular, 2(N-1) x N,
+ * and every one of them -- B1_t, B2_t (heateq.py:45-48), their transposes (:52-54),
+ * the mass inverse of Y (:57-63) -- is one 2 x 2 block per element.  A rank that owns
+ * the nodes [t_begin, t_end) holds the elements [max(t_begin-1, 0), min(t_end, N-1));
+ * its test-space slab is y[i*ld_y + 2*e_loc + a] with ld_y = 2*n_el (no padding: an
+ * element is one aligned 16-byte pair).  With t_begin > 0 the first element is a copy
+ * of the lower neighbour's last one, computed by both ranks with the same
+ * instructions; inner products skip it.  `first_node` is the local node index of the
+ * first held element's first node: -1 (the ghost row below the slab; t_begin > 0) or 0.
+ * blocks: 4*n_el device doubles per term, blk[4*e_loc + 2*a + b], 16-byte aligned.
+ *
+ * These entry points are the TIME side; the space factors are applied by the caller
+ * with the row engine (one stk_ell_spmm pass per matrix).  They replace the time
+ * factor of KronLinOp (linop.py:6-15) for B = B1_t kron M_x + B2_t kron A_x
+ * (heateq.py:45-54), for B^T (:52-54, :93-102: f = B^T K g + u0) and for the time
+ * factor of K = Minv_Y kron Kinv_x (:57-63) in the Y' estimator (:154-155).
+ *
+ * forward:   z_host[k] = X_k x on the node slab (M x ld_z, n_loc local nodes),
+ *            zg_host[k] = X_k applied to the interleaved ghost pair (M x 2; needed when
+ *            an element reaches the node -1 or the node n_loc; else NULL).  With z0, z1 the
+ *            two nodes of element e,
+ *              acc_a = 0; for k ascending: acc_a = fma(blk_k[e][a][1], z1_k, fma(blk_k[e][a][0], z0_k, acc_a));
+ *              y_{e,a} = beta == 0 ? acc_a : fma(beta, y_{e,a}, acc_a)     (non-temporal stores)
+ * transpose: w_host[k] = X_k^T y on the test-space slab (M x 2*n_el).  Node n adds the
+ *            element n-1 (where it is the second node), then the element n (the first):
+ *              acc = 0; for k ascending, for e in (n-1, n) that exist, a = 0, 1:
+ *                acc = fma(blk_k[e][a][n-e], w_k[e,a], acc);
+ *              x_n = beta == 0 ? acc : fma(beta, x_n, acc); the padding column of x is zero.
+ *            Both elements of every local node are held (the overlap): no exchange.
+ * block mix: y_{e,a} = fma(blk[e][a][1], x_{e,1}, blk[e][a][0] * x_{e,0}) on a test-space
+ *            slab; y may be x.
+ * The order of the sums depends on the element alone: results do not depend on the
+ * number of ranks.  At most STK_ELEM_MAX_TERMS terms. */
+#define STK_ELEM_MAX_TERMS 3
+int stk_elem_time_apply(void *stream, int32_t M, int32_t n_el, int32_t n_loc,
+                        int32_t ld_z, int32_t first_node, int32_t n_terms,
+                        const double *const *z_host, const double *const *zg_host,
+                        const double *const *blocks_host, double beta, double *y);
+int stk_elem_time_apply_t(void *stream, int32_t M, int32_t n_el, int32_t n_loc,
+                          int32_t ld_x, int32_t first_node, int32_t n_terms,
+                          const double *const *w_host,
+                          const double *const *blocks_host, double beta, double *x);
+int stk_elem_block_mix(void *stream, int32_t M, int32_t n_el, const double *blocks,
+                       const double *x, double *y);
+
+/* The same two maps FUSED with their space factors, in one pass over a packed slot
+ * stream (stk_pack_pattern with a dictionary, rows_per_unit 1 or 2; csrc/kron_pack_elem.hip):
+ *   forward:    y_{e,a} = sum_k sum_b blk_k[e][a][b] (X_{t[k].mat} x)_{node(e)+b}
+ *   transpose:  x_n = sum_k (element n-1, then n) sum_a blk_k[e][a][n-e] (X_{t[k].mat} y)_{e,a}
+ * (the space factors themselves are not transposed: symmetric matrices, as M_x and A_x).
+ * The walk and the gathers are those of stk_kron_pack_apply -- persistent workgroups on
+ * XCD-interleaved row groups, one lane per 16-byte pair, forward with the ghost lane on
+ * the interleaved `ghosts` (needed when an element reaches the node -1 or n_loc, else
+ * NULL) -- the space sums stay in LDS, and the time stage writes one 16-byte pair per
+ * element (forward) or per two nodes (transpose) with non-temporal stores.  Every row's
+ * space sums accumulate in ascending column order from zero; the time stage adds its
+ * products in the order written down above for the composed forms, which give the same
+ * doubles.  t[k].tri is ignored.  Exactly 2 terms (B = B1 + B2, heateq.py:52-53); x (y_in)
+ * must not alias y (x_out); slabs 16-byte aligned, ld even.
+ * Slab length: a workgroup keeps all 8*n_el block doubles, the dictionary and, per slot
+ * row it serves, 2 * rows_per_unit sums per node (forward) or per test-space column
+ * (transpose) in LDS, and a slot row needs at most 512 lanes.  The host function
+ * stk_kron_pack_elem_lds_bytes returns the bytes for ONE slot row at a time (host; reads
+ * K, n_codes and rows_per_unit of the pattern only), -1 where the lanes do not suffice;
+ * the fused calls serve a slab iff that is within 65536 -- with row pairs about 680
+ * nodes forward and 500 elements transposed -- and fail otherwise: the caller takes the
+ * composed forms above (ElementKronMatMPI asks first). */
+int64_t stk_kron_pack_elem_lds_bytes(const stk_pack_pattern *pattern_host, int32_t n_el,
+                                     int32_t n_loc, int32_t transposed);
+int stk_kron_pack_elem_apply(void *stream, const stk_pack_pattern *pattern_host,
+                             int32_t n_el, int32_t n_loc, int32_t ld,
+                             int32_t first_node, int32_t n_terms,
+                             const stk_kron_pack_term *terms_host,
+                             const double *const *blocks_host, const double *x,
+                             const double *ghosts, double beta, double *y);
+int stk_kron_pack_elem_apply_t(void *stream, const stk_pack_pattern *pattern_host,
+                               int32_t n_el, int32_t n_loc, int32_t ld,
+                               int32_t first_node, int32_t n_terms,
+                               const stk_kron_pack_term *terms_host,
+                               const double *const *blocks_host, const double *y_in,
+                               double beta, double *x_out);
+
 /* ---- wavelet transform in time, whole time axis on this GPU ---------------
  * y = (W_t kron I) x or (W_t^T kron I) x in the interleaved numbering, all
  * J levels in one pass (WaveletTransformOp._matmat / _rmatmat,

@@ -20,7 +20,8 @@ import scipy.sparse as sp
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from source.assembly import (space_load, space_matrices,  # noqa: E402
-                             time_matrices, time_matrices_test_space)
+                             time_load_test_space, time_matrices,
+                             time_matrices_test_space)
 from source.linalg import PCG  # noqa: E402
 from source.linop import (BlockDiagLinOp, CompositeLinOp,  # noqa: E402
                           DeviceLinearOperator, InvLinOp, KronLinOp,
@@ -89,10 +90,12 @@ class HeatEquation:
             matvec=lambda v: self.BT @ (self.K @ (self.B @ v)) + self.G @ v)
         self.WT_S_W = self.WT @ self.S @ self.W
 
-        # right-hand side (heateq.py:93-106); the model problems have no
-        # forcing (data['g'] is empty)
-        assert not data['g'], 'forcing terms are not wired'
+        # right-hand side (heateq.py:93-106): g = sum of the separable pairs of
+        # data['g'] (none for the homogeneous model problems)
         self.g_vec = np.zeros(self.K.shape[0])
+        for g_t, g_x in data['g']:
+            self.g_vec += np.kron(time_load_test_space(mesh_time, g_t),
+                                  space_load(mesh_space, g_x))
         self.u0_x = space_load(mesh_space, data['u0'])
         self.f = self.BT @ (self.K @ self.g_vec) + np.kron(u0_t, self.u0_x)
 
@@ -120,7 +123,7 @@ class HeatEquation:
 
 
 _OPTIONS = (
-    ('problem', str, 'square', 'problem type (square, lshape, cube)'),
+    ('problem', str, 'square', 'problem type (square, lshape, cube, square_forced, cube_forced)'),
     ('J_time', int, 5, 'number of time refines'),
     ('J_space', int, 6, 'number of space refines'),
     ('precond', str, 'multigrid', 'spatial preconditioner: multigrid or direct.'),

@@ -27,9 +27,10 @@ from source.comm import MPI
 from source.linalg import PCG
 from source.linop import (CompositeLinOp, EllMatrices, InvLinOp, as_space_op,
                           time_factor_steps)
-from source.mpi_kron import (BlockDiagMPI, CompositeMPI, LinearOperatorMPI,
-                             MatKronIdentityMPI, SumMPI, TridiagKronMatMPI,
-                             _FusedKronSum, _local_tridiag)
+from source.mpi_kron import (BlockDiagMPI, CompositeMPI, ElementKronMatMPI,
+                             LinearOperatorMPI, MatKronIdentityMPI, SumMPI,
+                             TridiagKronMatMPI, _FusedKronSum, _local_tridiag,
+                             element_block_mix)
 from source.mpi_vector import DofDistributionMPI, KronVectorMPI
 from source.multigrid import MeshHierarchy, MultiGrid, MultiGridFamily
 from source.problem import problem_helper
@@ -271,7 +272,6 @@ class HeatEquationMPI:
         mark('time and space matrices')
         self.N = self.A_t.shape[0]
         self.M = self.M_x.shape[0]
-        assert (len(data['g']) == 0)
         self.dofs_distr = DofDistributionMPI(comm, self.N, self.M)
 
         # --- Wavelet transform --- (heateq_mpi.py:126-139)
@@ -401,6 +401,11 @@ class HeatEquationMPI:
             _lib.stream(), self.M, self.rhs.n_loc, self.rhs.ld, _lib.ptr(u_t),
             _lib.ptr(u_x), _lib.ptr(self.rhs.buf)))
 
+        # -- forcing -- (serial heateq.py:93-102; asserted away in heateq_mpi.py:99)
+        self.g = self.f = self.B = self._BT = self.dofs_test = None
+        if data['g']:
+            self._set_up_forcing(mesh_time, mesh_space, data['g'])
+
         from source.linop import forget_union_pattern
         forget_union_pattern()
         if hasattr(self.hierarchy, 'forget'):
@@ -426,6 +431,79 @@ class HeatEquationMPI:
         plans.set_option('fuse_restrict_max_level', J - 1 if acc['fuse_restrict_below_finest'] else -1)
         plans.set_option('fast_until_cycle', vcycles - 1 if acc['fast_leading_cycles'] else 0)
         plans.set_option('fast_parts', acc['fast_parts'])
+
+    def _set_up_forcing(self, mesh_time, mesh_space, pairs):
+        """g = sum g_t kron g_x on the test-space slab and f = B^T K g + u0_t kron u0_x
+        (reference heateq.py:93-102), with B and B^T on time slabs
+        (mpi_kron.ElementKronMatMPI, on the plan S streams where S has one) and
+        K = Minv_Y kron Kinv_x on the driver's own Kinv_x.  In f, Minv_Y is folded into
+        the blocks of B^T on the host -- B_k^T Minv_Y is again one 2 x 2 block per
+        element, (Minv_Y[e] B_k[e])^T -- so B^T K g = E^T (blocks') (I kron Kinv_x) g is
+        one multigrid apply and one element pass; arithmetic='reference' applies K, then
+        the plain B^T.  `BT` itself is built when somebody asks for it."""
+        from source.assembly import (element_blocks, time_load_test_space,
+                                     time_matrices_test_space)
+        _, Minv_Y, B1_t, B2_t = time_matrices_test_space(mesh_time)
+        b1, b2, minv = element_blocks(B1_t), element_blocks(B2_t), element_blocks(Minv_Y)
+        dd = self.dofs_distr
+        # M_x and A_x are symmetric by construction; the plan of (M_x, A_x) is S's
+        self._element_op = lambda blocks, transposed: ElementKronMatMPI(
+            dd, blocks, [self.M_x, self.A_x], transposed=transposed, symmetric=True,
+            ell=getattr(self.S, 'ell', None))
+        self._b_blocks = [b1, b2]
+        self.B = self._element_op(self._b_blocks, False)
+        self.dofs_test = dt = self.B.dofs_test
+        self._minv_blocks = _lib.to_dev(minv[dt.e_begin:dt.e_end])
+        self.g = KronVectorMPI(dt)
+        lib, part = _lib.lib(), None
+        for k, (g_t, g_x) in enumerate(pairs):
+            l_t = _lib.to_dev(time_load_test_space(mesh_time, g_t)[dt.t_begin:dt.t_end])
+            l_x = _lib.to_dev(space_load(mesh_space, g_x))
+            if k and part is None:
+                part = KronVectorMPI(dt)
+            into = part if k else self.g
+            _lib.check(lib.stk_outer(_lib.stream(), self.M, into.n_loc, into.ld, _lib.ptr(l_t),
+                                     _lib.ptr(l_x), _lib.ptr(into.buf)))
+            if k:
+                self.g += part
+        if self.arithmetic == 'reference':
+            self.f = self.BT @ self.K_Y(self.g)
+        else:
+            BT_Minv = self._element_op([minv @ b1, minv @ b2], True)
+            self.f = BT_Minv @ KronVectorMPI.around(dt, self.Kinv_x.apply(self.g.buf, n_loc=self.g.n_loc))
+        self.f += self.rhs
+
+    @property
+    def BT(self):
+        """B^T (test space -> nodes) of a problem with forcing, None without; built on
+        first use -- the default arithmetic forms f through the blocks with Minv_Y folded
+        in and never needs it."""
+        if self._BT is None and self.B is not None:
+            self._BT = self._element_op(self._b_blocks, True)
+        return self._BT
+
+    def K_Y(self, y):
+        """K = Minv_Y kron Kinv_x on a test-space vector (reference heateq.py:57-63), as a
+        new vector: the space factor into a new slab, the block mix of the time factor in
+        place on it (the two factors act on different indices)."""
+        out = self.Kinv_x.apply(y.buf, n_loc=y.n_loc)
+        return KronVectorMPI.around(self.dofs_test, element_block_mix(self.dofs_test, self._minv_blocks, out))
+
+    def solve(self, callback=None, history=None):
+        """PCG on the wavelet-transformed system with the forcing's right-hand side
+        (reference heateq.py:146-150); returns (u = W w, iterations)."""
+        assert self.f is not None, 'solve() is the path of a problem with forcing; without: PCG on rhs'
+        w, iters = PCG(self.WT_S_W, self.P, self.WT @ self.f, callback=callback, history=history)
+        return self.W @ w, iters
+
+    def errors(self, u):
+        """(algebraic error r.Pr of u in the X-norm with r = f - S u, error in Y'
+        (g - B u)^T K (g - B u)): the two numbers of the serial driver's last line
+        (reference heateq.py:151-155)."""
+        assert self.f is not None
+        residual = self.f - self.S @ u
+        defect = self.g - self.B @ u
+        return residual.dot(self.P @ residual), defect.dot(self.K_Y(defect))
 
     def print_time_per_apply(self):
         for name in driver.OPERATORS:
@@ -469,8 +547,11 @@ def main(argv=None):
     comm.Barrier()
     began = MPI.Wtime()
     history = []
-    solution, iters = PCG(heat.WT_S_W, heat.P, heat.rhs, callback=progress,
-                          history=history)
+    if heat.f is None:
+        solution, iters = PCG(heat.WT_S_W, heat.P, heat.rhs, callback=progress,
+                              history=history)
+    else:
+        solution, iters = heat.solve(callback=progress, history=history)
     comm.Barrier()
     record.update(solve_time=MPI.Wtime() - began, mem_after_solve=mem(),
                   iters=iters, r_dot_Pr=list(history),
@@ -490,6 +571,13 @@ def main(argv=None):
         print('Final r.Pr: %s' % history[-1])
         heat.print_time_per_apply()
         print('Device memory after solve: %smb.' % mem())
+    if heat.f is not None:
+        # the serial driver's last line (reference heateq.py:156-158); collective
+        error_alg, error_Yprime = heat.errors(solution)
+        record.update(error_alg=error_alg, error_Yprime=error_Yprime)
+        if rank == 0:
+            print('Done in %d  PCG steps. X-norm algebraic error: %s. Error in Yprime: %s\n'
+                  % (iters, error_alg, error_Yprime))
     driver.publish(comm, record)
     return heat, solution, iters, history
 

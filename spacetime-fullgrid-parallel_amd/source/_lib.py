@@ -217,6 +217,23 @@ _PROTOTYPES = {
     'stk_time_dense_apply': (ctypes.c_int, [
         c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p
     ]),
+    'stk_elem_time_apply': (ctypes.c_int, [
+        c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_p), ctypes.POINTER(c_p),
+        ctypes.POINTER(c_p), c_f64, c_p
+    ]),
+    'stk_elem_time_apply_t': (ctypes.c_int, [
+        c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_f64, c_p
+    ]),
+    'stk_kron_pack_elem_lds_bytes': (c_i64, [ctypes.POINTER(PackPattern), c_i32, c_i32, c_i32]),
+    'stk_kron_pack_elem_apply': (ctypes.c_int, [
+        c_p, ctypes.POINTER(PackPattern), c_i32, c_i32, c_i32, c_i32, c_i32,
+        ctypes.POINTER(KronPackTerm), ctypes.POINTER(c_p), c_p, c_p, c_f64, c_p
+    ]),
+    'stk_kron_pack_elem_apply_t': (ctypes.c_int, [
+        c_p, ctypes.POINTER(PackPattern), c_i32, c_i32, c_i32, c_i32, c_i32,
+        ctypes.POINTER(KronPackTerm), ctypes.POINTER(c_p), c_p, c_f64, c_p
+    ]),
+    'stk_elem_block_mix': (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_p, c_p]),
     'stk_wavelet_apply': (ctypes.c_int,
                           [c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
     'stk_mg_create': (ctypes.c_int, [

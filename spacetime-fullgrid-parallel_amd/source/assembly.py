@@ -85,6 +85,44 @@ def time_matrices_test_space(mesh_time):
     return M_Y, Minv_Y, B1_t, B2_t
 
 
+def time_load_test_space(mesh_time, fn, nq=4):
+    """int fn * psi_{e,a} for the two nodal functions of every time element, in the
+    ordering 2e + a of time_matrices_test_space: the time factor of the forcing's load
+    vector (reference heateq.py:93-100, `LinearForm(g_t * v * dx)` on the test space).
+    Gauss-Legendre with `nq` points per element (exact up to degree 2 nq - 1 for
+    fn * psi).  NGSolve chooses the integration order of a coefficient function
+    itself and that choice cannot be pinned from here, so this vector agrees with the
+    reference's up to the quadrature error of both, not to rounding."""
+    n, h = mesh_time.nv, mesh_time.h
+    ne = n - 1
+    q, w = np.polynomial.legendre.leggauss(nq)
+    s = 0.5 * (q + 1.0)  # points on [0, 1]
+    t = h * (np.arange(ne)[:, None] + s[None, :])  # (ne, nq)
+    f = fn(t) * (0.5 * h * w)[None, :]
+    out = np.empty(2 * ne)
+    out[0::2] = f @ (1.0 - s)
+    out[1::2] = f @ s
+    return out
+
+
+def element_blocks(mat_time):
+    """(ne, 2, 2) blocks blk[e][a][b] = mat[2e + a, e + b] of a time factor from the
+    nodes to the test space (B1_t, B2_t of time_matrices_test_space), or
+    mat[2e + a, 2e + b] of a block-diagonal one on the test space (M_Y, Minv_Y); every
+    other entry must be zero."""
+    mat = sp.csr_matrix(mat_time)
+    ne = mat.shape[0] // 2
+    assert mat.shape[0] == 2 * ne and mat.shape[1] in (ne + 1, 2 * ne), mat.shape
+    step = 1 if mat.shape[1] == ne + 1 else 2
+    e = np.arange(ne)
+    blk = np.empty((ne, 2, 2))
+    for a in (0, 1):
+        for b in (0, 1):
+            blk[:, a, b] = np.asarray(mat[2 * e + a, step * e + b]).reshape(-1)
+    assert mat.count_nonzero() == np.count_nonzero(blk), 'entries outside the element blocks'
+    return blk
+
+
 # ----------------------------------------------------------------------------
 # Space: P1 on a triangulation (d = 2) or a tetrahedral mesh (d = 3).
 # ----------------------------------------------------------------------------

@@ -15,7 +15,7 @@ from .comm import MPI
 
 # (flag, type, default, help): the options both reference drivers take
 _PROBLEM_OPTIONS = (
-    ('problem', str, 'square', 'problem type (square, lshape, cube)'),
+    ('problem', str, 'square', 'problem type (square, lshape, cube, square_forced, cube_forced)'),
     ('J_time', int, 7, 'number of time refines'),
     ('J_space', int, 7, 'number of space refines'),
     ('smoothsteps', int, 3, 'number of smoothing steps'),

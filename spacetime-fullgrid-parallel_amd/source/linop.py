@@ -980,6 +980,25 @@ class PackedEllMatrices:
             _lib.stream(), ctypes.byref(self.pattern), n_loc, ld, len(specs),
             terms, xs, t0, t1, beta, _lib.ptr(out)))
 
+    def apply_elem(self, mats, blocks, x, ghosts, n_el, n_loc, ld, first_node, beta, out, transposed=False):
+        """The element-block sums between a node slab and a test-space slab on the packed
+        stream (stk_kron_pack_elem_apply / _t): term k = (matrix mats[k] of the plan, the
+        device blocks blocks[k] of its time factor).  Forward: x node slab (ld), `ghosts`
+        the interleaved pair or None, out the test-space slab; transposed: x the test-space
+        slab, out the node slab (ld).  The dictionary form only."""
+        assert not self.explicit
+        terms = self._terms([(None, k) for k in mats])
+        blk = (ctypes.c_void_p * len(blocks))(*[_lib.ptr(b) for b in blocks])
+        lib = _lib.lib()
+        if transposed:
+            _lib.check(lib.stk_kron_pack_elem_apply_t(
+                _lib.stream(), ctypes.byref(self.pattern), n_el, n_loc, ld, first_node, len(mats), terms, blk,
+                _lib.ptr(x), beta, _lib.ptr(out)))
+        else:
+            _lib.check(lib.stk_kron_pack_elem_apply(
+                _lib.stream(), ctypes.byref(self.pattern), n_el, n_loc, ld, first_node, len(mats), terms, blk,
+                _lib.ptr(x), _lib.ptr(ghosts), beta, _lib.ptr(out)))
+
     def apply(self, specs, x, ghosts, n_loc, ld, beta, out):
         """y = beta*y + sum over specs (tri, matrix index) applied to x;
         `ghosts`: (M, 2) interleaved ghost time steps or None."""

@@ -19,7 +19,8 @@ import torch
 from . import _lib
 from .comm import MPI
 from .linop import SpaceMatrix, SpaceOp, as_space_op
-from .mpi_vector import DofDistributionMPI, KronVectorMPI
+from .mpi_vector import (DofDistributionMPI, KronVectorMPI,
+                         ElementDistributionMPI)
 
 
 def as_matrix(operator):
@@ -51,7 +52,7 @@ class LinearOperatorMPI:
         assert isinstance(x, KronVectorMPI)
         if not LinearOperatorMPI.sync_timing:
             start_time = MPI.Wtime()
-            y = self._matvec(x, x._like())
+            y = self._matvec(x, self._new_output(x))
             self.num_applies += 1
             self.time_applies += MPI.Wtime() - start_time  # enqueue time only
             return y
@@ -61,12 +62,16 @@ class LinearOperatorMPI:
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
-        y = self._matvec(x, x._like())
+        y = self._matvec(x, self._new_output(x))
         e1.record()
         e1.synchronize()
         self.num_applies += 1
         self.time_applies += e0.elapsed_time(e1) * 1e-3
         return y
+
+    def _new_output(self, x):
+        """The vector _matvec writes (operators between two spaces override it)."""
+        return x._like()
 
     def time_per_apply(self):
         assert (self.time_applies)
@@ -563,6 +568,179 @@ class _FusedKronSum:
             self.needs_hi and self.dofs_distr.rank + 1 < self.dofs_distr.size)
         return (16 * n_loc * M + 8 * h * M + 12 * sum(self.nnz_terms) +
                 4 * (M + 1) * len(self.nnz_terms))
+
+
+def _ptr_array(tensors):
+    """Host array of device pointers (None -> NULL), as the *_host arguments take."""
+    arr = (ctypes.c_void_p * len(tensors))()
+    for k, t in enumerate(tensors):
+        arr[k] = _lib.ptr(t)
+    return arr
+
+
+class ElementKronMatMPI(LinearOperatorMPI):
+    """sum_k (T_k kron X_k) for time factors T_k between the nodes and the TEST space
+    (discontinuous P1 in time: 2 (N - 1) x N, one 2 x 2 block per element), as B =
+    B1_t kron M_x + B2_t kron A_x of the serial driver (reference heateq.py:45-54) --
+    on time slabs, where the reference's time-parallel driver has no B at all.
+
+    ``blocks_per_term[k]``: (N - 1, 2, 2), blk[e][a][b] = T_k[2e + a, e + b]
+    (assembly.element_blocks); ``mats_space[k]``: the CSR space factor.  It maps a node
+    vector (KronVectorMPI on `dofs_distr`) to a test-space vector (on
+    ElementDistributionMPI(dofs_distr)); ``transposed=True``: the transpose, test
+    space to nodes -- sum_k (T_k^T kron X_k^T), the blocks given as for the forward map.
+
+    Two forms, the same doubles.  FUSED (csrc/kron_pack_elem.hip,
+    stk_kron_pack_elem_apply / _t): one pass over the packed slot stream of the shared
+    EllMatrices plan of the space factors -- two terms, symmetric space factors, a plan
+    with a dictionary (square, L-shape, cube).  COMPOSED, for everything else (the
+    jittered L-shape has no dictionary) and as the comparison partner: every space
+    factor through the row engine (stk_ell_spmm: on the slab, and forward also on the
+    interleaved pair of ghost rows), then ONE time stage over all terms
+    (stk_elem_time_apply / _t, csrc/kron_elem.hip).  Forward reads the two ghost rows of
+    communicate_bdr; the transpose exchanges nothing (every local node holds both its
+    elements).  Results do not depend on the number of ranks."""
+    use_fused = True  # False: always the composed form
+
+    def __init__(self, dofs_distr, blocks_per_term, mats_space, transposed=False, symmetric=None, ell=None):
+        """symmetric: whether every space factor equals its transpose (None: looked up
+        here, one sparse difference per matrix -- a caller that knows, as the driver does
+        of M_x and A_x, says so); ell: the EllMatrices plan of exactly `mats_space`, in
+        this order, where the caller holds it (the driver: the plan S streams; None: the
+        shared plan of these matrices, built if nobody holds it any more)."""
+        super().__init__(dofs_distr)
+        assert 1 <= len(blocks_per_term) == len(mats_space) <= 3
+        self.dofs_test = ElementDistributionMPI(dofs_distr)
+        self.transposed = bool(transposed)
+        dt = self.dofs_test
+        self._blocks_host = [np.ascontiguousarray(b, dtype=np.float64) for b in blocks_per_term]
+        for b in self._blocks_host:
+            assert b.shape == (dt.n_elements, 2, 2), b.shape
+        self.blocks = [_lib.to_dev(b[dt.e_begin:dt.e_end]) for b in self._blocks_host]
+        self.mats_space = [scipy.sparse.csr_matrix(m) for m in mats_space]
+        if symmetric is None:
+            symmetric = all((abs(m - m.T) > 0).nnz == 0 for m in self.mats_space)
+        self._symmetric = bool(symmetric)
+        # the space factors of the transpose are the transposed matrices; symmetric ones
+        # (M_x, A_x) keep their uploaded copies
+        self.space_ops = [as_space_op(m if self._symmetric or not self.transposed else scipy.sparse.csr_matrix(m.T))
+                          for m in mats_space]
+        assert all(isinstance(op, SpaceMatrix) for op in self.space_ops)
+        self._ell = ell
+        self._fused = {}  # use_fused -> the plan fused_plan found (decided once per setting)
+
+    LDS_BYTES = 64 * 1024  # of a workgroup (csrc/kron_pack_elem.hip)
+
+    @classmethod
+    def fused_fits(cls, pattern, n_el, n_loc, transposed):
+        """Whether the fused kernels serve a slab of n_loc nodes and n_el elements on the
+        packed pattern (a _lib.PackPattern; K, n_codes and rows_per_unit are read): by the
+        kernel's own count of lanes and of LDS for one slot row at a time
+        (stk_kron_pack_elem_lds_bytes; host code, no device needed)."""
+        need = _lib.lib().stk_kron_pack_elem_lds_bytes(ctypes.byref(pattern), n_el, n_loc, int(bool(transposed)))
+        return 0 <= need <= cls.LDS_BYTES
+
+    def fused_plan(self):
+        """The packed plan the fused kernels stream, None: the composed form."""
+        key = bool(type(self).use_fused)
+        if key not in self._fused:
+            self._fused[key] = self._find_fused_plan() if key else None
+        return self._fused[key]
+
+    def _find_fused_plan(self):
+        if len(self.blocks) != 2 or not self._symmetric:
+            return None
+        dd, dt = self.dofs_distr, self.dofs_test
+        n_loc = dd.t_end - dd.t_begin
+        if self._ell is None:
+            from .linop import EllMatrices
+            self._ell = EllMatrices.shared(self.mats_space)
+        packed = self._ell.packed_for(n_loc)
+        if not packed.ok or packed.explicit:
+            return None
+        # long slabs: the element blocks and the sums of one slot row outgrow the LDS
+        return packed if self.fused_fits(packed.pattern, dt.n_el, n_loc, self.transposed) else None
+
+    def _new_output(self, x):
+        return KronVectorMPI(self.dofs_distr if self.transposed else self.dofs_test)
+
+    def apply_buf(self, x_buf, ghosts, out, beta=0.0):
+        """The local kernels on slab tensors: forward (x_buf: node slab, ghosts: the
+        interleaved (M, 2) pair or None, out: test-space slab) or transposed."""
+        dd, dt = self.dofs_distr, self.dofs_test
+        n_loc = dd.t_end - dd.t_begin
+        lib, n_terms = _lib.lib(), len(self.blocks)
+        packed = self.fused_plan()
+        if packed is not None:
+            packed.apply_elem(range(n_terms), self.blocks, x_buf, ghosts, dt.n_el, n_loc,
+                              n_loc + (n_loc & 1), dt.first_node, beta, out, transposed=self.transposed)
+            return out
+        if self.transposed:
+            w = [op.apply(x_buf, n_loc=2 * dt.n_el) for op in self.space_ops]
+            _lib.check(lib.stk_elem_time_apply_t(
+                _lib.stream(), self.M, dt.n_el, n_loc, out.shape[1], dt.first_node, n_terms,
+                _ptr_array(w), _ptr_array(self.blocks), beta, _lib.ptr(out)))
+            return out
+        z = [op.apply(x_buf, n_loc=n_loc) for op in self.space_ops]
+        zg = [None if ghosts is None else op.apply(ghosts, n_loc=2) for op in self.space_ops]
+        _lib.check(lib.stk_elem_time_apply(
+            _lib.stream(), self.M, dt.n_el, n_loc, x_buf.shape[1], dt.first_node, n_terms,
+            _ptr_array(z), _ptr_array(zg), _ptr_array(self.blocks), beta, _lib.ptr(out)))
+        return out
+
+    def _matvec(self, vec_in, vec_out):
+        assert isinstance(vec_in, KronVectorMPI) and vec_in is not vec_out
+        src = self.dofs_test if self.transposed else self.dofs_distr
+        assert (vec_in.N, vec_in.M, vec_in.t_begin) == (src.N, src.M, src.t_begin), 'vector of the other space'
+        ghosts = None
+        if not self.transposed and self.dofs_distr.size > 1:
+            self.time_communication += vec_in.communicate_bdr()
+            ghosts = vec_in.ghost_interleaved()
+        self.apply_buf(vec_in.buf, ghosts, vec_out.buf)
+        vec_out.communicated_bdr = False
+        return vec_out
+
+    def as_matrix(self):
+        """sum_k T_k kron X_k (or its transpose) as a dense host matrix, from the blocks."""
+        dt = self.dofs_test
+        total = 0.0
+        for blk, X in zip(self._blocks_host, self.mats_space):
+            T = np.zeros((dt.N, self.N))
+            for e in range(dt.n_elements):
+                T[2 * e:2 * e + 2, e:e + 2] = blk[e]
+            total = total + np.kron(T, X.toarray())
+        return total.T if self.transposed else total
+
+    def as_global_matrix(self):
+        """Applies the operator to every unit vector of its domain (reference
+        mpi_kron.py:38-59, between two spaces).  Expensive: tests only."""
+        src, dst = ((self.dofs_test, self.dofs_distr) if self.transposed else
+                    (self.dofs_distr, self.dofs_test))
+        n_in, n_out = src.N * self.M, dst.N * self.M
+        rank = self.dofs_distr.comm.Get_rank()
+        result = y_glob = None
+        if rank == 0:
+            y_glob, result = np.empty(n_out), np.zeros((n_out, n_in))
+        unit = np.zeros(n_in)
+        for k in range(n_in):
+            unit[k] = 1.0
+            x_mpi = KronVectorMPI(src)
+            x_mpi.scatter(unit if rank == 0 else None)
+            unit[k] = 0.0
+            (self @ x_mpi).gather(y_glob)
+            if rank == 0:
+                result[:, k] = y_glob
+        return result
+
+
+def element_block_mix(dofs_test, blocks_dev, buf, out=None):
+    """(T kron I) on a test-space slab for a block-diagonal T on the test space (Minv_Y,
+    reference heateq.py:57-62), given as the local (n_el, 2, 2) device blocks
+    (stk_elem_block_mix); in place unless `out` is given."""
+    out = buf if out is None else out
+    _lib.check(_lib.lib().stk_elem_block_mix(_lib.stream(), dofs_test.M, dofs_test.n_el,
+                                             _lib.ptr(blocks_dev), _lib.ptr(buf), _lib.ptr(out)))
+    return out
 
 
 class SparseKronIdentityMPI(LinearOperatorMPI):

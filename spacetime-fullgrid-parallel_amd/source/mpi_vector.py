@@ -50,6 +50,37 @@ class DofDistributionMPI:
             self.dof2proc[t_begin:t_end] = p
 
 
+class ElementDistributionMPI:
+    """The time dofs of the TEST space over the ranks of a node distribution.  The test
+    space is discontinuous P1 in time (reference heateq.py:36): two dofs 2e + a per
+    time element, 2 (N - 1) columns in all.  The rank that owns the nodes
+    [t_begin, t_end) HOLDS the elements [max(t_begin - 1, 0), min(t_end, N - 1)); with
+    t_begin > 0 the first of them is a copy of the lower neighbour's last element,
+    computed by both with the same instructions (include/stk.h "test-space slabs").
+    With this overlap B^T needs no exchange and B the two ghost rows of
+    communicate_bdr; no rank holds an empty slab; `copied_columns` tells dot to leave
+    the copy out, so element e counts on the rank that owns node e.
+
+    Quacks like DofDistributionMPI for KronVectorMPI: t_begin / t_end are the HELD
+    columns (dof_distribution: those of every rank, overlapping by two)."""
+    def __init__(self, nodes):
+        assert nodes.N >= 2
+        self.nodes = nodes
+        self.comm, self.rank, self.size, self.M = nodes.comm, nodes.rank, nodes.size, nodes.M
+        self.n_elements = nodes.N - 1
+        self.N = 2 * self.n_elements
+        held = [(max(b - 1, 0), min(e, self.n_elements)) for b, e in nodes.dof_distribution]
+        self.dof_distribution = [[2 * b, 2 * e] for b, e in held]
+        self.e_begin, self.e_end = held[self.rank]
+        self.n_el = self.e_end - self.e_begin
+        assert self.n_el >= 1
+        self.t_begin, self.t_end = self.dof_distribution[self.rank]
+        self.copied_columns = 2 if nodes.t_begin > 0 else 0
+        # local node index of the first held element's first node: -1 = the ghost row
+        self.first_node = -1 if nodes.t_begin > 0 else 0
+        self.dof2proc = np.repeat(nodes.dof2proc[:self.n_elements], 2)
+
+
 def _fill_slab(buf, n_loc, src):
     """buf[i, t] = src[t, i] for a time-major (n_loc, M) block `src` (padding
     columns zero).  On the device: libstk's tiled transpose (stk_transpose); host
@@ -444,11 +475,19 @@ class KronVectorMPI:
         axis, bit for bit; one D2H read of N doubles."""
         assert (isinstance(vec_other, KronVectorMPI))
         assert (vec_other.buf.shape == self.buf.shape)
-        work, steps = _dot_workspace(self.buf.device, self.M, self.n_loc, self.N, self.t_begin)
-        _lib.check(_lib.lib().stk_slab_dot(
-            _lib.stream(), self.M, self.n_loc, self.ld, _lib.ptr(self.buf),
-            _lib.ptr(vec_other.buf), _lib.ptr(work), self.N, self.t_begin,
-            _lib.ptr(steps)))
+        # leading columns that are a copy of the neighbour's (test-space slabs,
+        # ElementDistributionMPI: an even number, so the rest stays 16-byte aligned)
+        # count on the neighbour
+        skip = getattr(self.dofs_distr, 'copied_columns', 0)
+        n_own, t_own = self.n_loc - skip, self.t_begin + skip
+        work, steps = _dot_workspace(self.buf.device, self.M, n_own, self.N, t_own)
+        if n_own > 0:
+            _lib.check(_lib.lib().stk_slab_dot(
+                _lib.stream(), self.M, n_own, self.ld, _lib.ptr(self.buf) + 8 * skip,
+                _lib.ptr(vec_other.buf) + 8 * skip, _lib.ptr(work), self.N, t_own,
+                _lib.ptr(steps)))
+        else:  # a rank that owns the last node and no element
+            steps.zero_()
         self.dofs_distr.comm.allreduce_tensor_(steps)
         total = 0.0
         for value in steps.tolist():  # increasing t, plain additions (stk_sum_steps)

@@ -5,6 +5,15 @@
 cube asserts there, problem.py:35-41); BASELINE.json config 4 names it, so it
 is defined here with the same data on the L-shaped domain.  ``cube``:
 u = exp(-3 pi^2 t) sin(pi x) sin(pi y) sin(pi z) on [0,1]^3 (problem.py:21-32).
+
+``square_forced`` / ``cube_forced``: manufactured solutions with a right-hand side,
+in the reference's shape for it (problem.py:13-17: ``data['g']`` is a list of
+separable pairs ``(g_t, g_x)`` of pointwise functions, g = sum g_t(t) g_x(x)).  With
+s_kl = sin(k pi x) sin(l pi y),
+    square:  u = exp(-t) s_11 + t s_21,   g = (2 pi^2 - 1) exp(-t) s_11 + (1 + 5 pi^2 t) s_21,
+    cube:    u = exp(-t) s_111 + t s_211, g = (3 pi^2 - 1) exp(-t) s_111 + (1 + 6 pi^2 t) s_211,
+u(0) = s_11 (s_111): two pairs whose space factors differ.  ``data['exact']`` is u
+as a function (t, x, y[, z]) of arrays, for the tests.
 """
 import numpy as np
 
@@ -66,6 +75,34 @@ def cube(J_space, J_time=None):
     return mesh_space, bc, _time_mesh(J_space, J_time), data, "cube"
 
 
+def _s21(x, y):
+    return np.sin(2 * np.pi * x) * np.sin(np.pi * y)
+
+
+def _s211(x, y, z):
+    return np.sin(2 * np.pi * x) * np.sin(np.pi * y) * np.sin(np.pi * z)
+
+
+def _forced_data(d, first, second):
+    """u = exp(-t) first + t second on [0,1]^d, where -laplace first = d pi^2 first
+    and -laplace second = (d + 3) pi^2 second: g = u_t - laplace u."""
+    pi2 = np.pi**2
+    g = [(lambda t: (d * pi2 - 1.0) * np.exp(-t), first),
+         (lambda t: 1.0 + (d + 3.0) * pi2 * t, second)]
+    exact = lambda t, *x: np.exp(-t) * first(*x) + t * second(*x)
+    return {'g': g, 'u0': first, 'exact': exact}
+
+
+def square_forced(J_space, J_time=None):
+    mesh_space, bc = construct_2d_square_mesh(nrefines=J_space)
+    return mesh_space, bc, _time_mesh(J_space, J_time), _forced_data(2, _u0, _s21), "square_forced"
+
+
+def cube_forced(J_space, J_time=None):
+    mesh_space, bc = construct_3d_cube_mesh(nrefines=J_space)
+    return mesh_space, bc, _time_mesh(J_space, J_time), _forced_data(3, _u0_3d, _s211), "cube_forced"
+
+
 def problem_helper(problem, J_space, J_time=None):
     if problem == 'square':
         return square(J_space, J_time)
@@ -75,5 +112,9 @@ def problem_helper(problem, J_space, J_time=None):
         return lshape_jitter(J_space, J_time)
     elif problem == 'cube':
         return cube(J_space, J_time)
+    elif problem == 'square_forced':
+        return square_forced(J_space, J_time)
+    elif problem == 'cube_forced':
+        return cube_forced(J_space, J_time)
     else:
         assert (False)
