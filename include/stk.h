@@ -1047,6 +1047,52 @@ int stk_p1_load_sum_2d(int64_t nv, int64_t nt, const double *points,
                        const double *rule_weights, const double *rule_points,
                        const double *f, double *vec);
 
+/* ---- space-time load vectors: int g(t_k, .) phi_i on the device ------------------
+ * A right-hand side g(t, x) that is no short separable sum needs one spatial load
+ * vector per time quadrature point, hundreds per problem; the two host calls above
+ * serve the single one of u0.  The plan is built once per mesh from HOST arrays:
+ * points [nv][d], cells [nc][d + 1] (d = 2 or 3), free_vertices [n_free] = the vertex
+ * of every slab row, and optionally row_order [n_free], a permutation of the rows
+ * in which the gather pass visits them (stk_tile_order's; a performance hint, results
+ * never depend on it; null = ascending).  It uploads them, computes |T| per cell by
+ * the expression of stk_p1_load_sum_2d (tetrahedra: the cofactor expansion of
+ * source/assembly.py) and builds for every free dof the list of its (cell, local
+ * vertex) incidences in ascending order.  max_k = the most time points one
+ * stk_load_columns call takes (1..STK_LOAD_MAX_K): the plan owns max_k * (d + 1) * nc
+ * doubles of workspace, so one plan serves one stream at a time.
+ *
+ * The rule is the caller's, per call, as HOST arrays in barycentric coordinates:
+ * rule_points [nq][d + 1], rule_weights [nq], 1 <= nq <= STK_LOAD_MAX_NQ.
+ * stk_load_points writes the DEVICE array q_points [d][nc][nq]: coordinate k of
+ * point q of cell t is l_q0 p0[k] + l_q1 p1[k] + ..., summed from the left -- the
+ * doubles of stk_p1_load_points_2d.
+ * stk_load_columns takes the DEVICE array f [n_k][nc][nq] (f at those points for n_k
+ * time points), HOST coefficients coef [n_k][2], and out_pair = the 16-byte aligned
+ * address of columns (2e, 2e + 1) of row 0 of a test-space slab with leading
+ * dimension ld (even), and writes for every free dof i and a = 0, 1
+ *     out_pair[i ld + a] (+)= sum_k coef[k][a] L_k[i],   k ascending, the first
+ *                              product starting the sum,
+ * where L_k is the vector stk_p1_load_sum_2d documents: the share of cell t in the
+ * entry of its local vertex a' is (sum_q (f_q w_q) l_qa') |T|, q ascending from 0.0,
+ * and an entry sums its shares in ascending (t, a') from 0.0.  accumulate = 0
+ * overwrites the pair, 1 adds the sum to what is there (old + sum).  Nothing else of
+ * the slab is touched.  No fused multiply-adds anywhere: bit for bit the doubles of
+ * the host routines combined on the host, whatever the launch shape. */
+#define STK_LOAD_MAX_NQ 16
+#define STK_LOAD_MAX_K 16
+typedef struct stk_load_plan stk_load_plan;
+int stk_load_plan_create(int32_t d, int64_t nv, int64_t nc, const double *points,
+                         const int64_t *cells, int64_t n_free,
+                         const int64_t *free_vertices, const int32_t *row_order,
+                         int32_t max_k, stk_load_plan **out);
+int stk_load_plan_destroy(stk_load_plan *plan);
+int stk_load_points(void *stream, const stk_load_plan *plan, int32_t nq,
+                    const double *rule_points, double *q_points);
+int stk_load_columns(void *stream, const stk_load_plan *plan, int32_t nq,
+                     const double *rule_weights, const double *rule_points,
+                     int32_t n_k, const double *f, const double *coef,
+                     int32_t accumulate, int32_t ld, double *out_pair);
+
 /* ---- plan construction on the host threads: processing order and union pattern ---
  * stk_tile_order: the mesh-tile order of n dofs with coordinates coords [n][d]
  * (d = 2 or 3): the bounding box cut into cubes of edge `side` from the corner `lo`

@@ -19,7 +19,8 @@ import numpy as np
 import scipy.sparse as sp
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from source.assembly import (space_load, space_matrices,  # noqa: E402
+from source.assembly import (DeviceLoadPlan, fill_test_space_slab,  # noqa: E402
+                             space_load, space_matrices,
                              time_load_test_space, time_matrices,
                              time_matrices_test_space)
 from source.linalg import PCG  # noqa: E402
@@ -91,11 +92,25 @@ class HeatEquation:
         self.WT_S_W = self.WT @ self.S @ self.W
 
         # right-hand side (heateq.py:93-106): g = sum of the separable pairs of
-        # data['g'] (none for the homogeneous model problems)
+        # data['g'] (none for the homogeneous model problems) and of its callables
+        # g(t, x, y[, z]), whose loads the device builds (the engine of heateq_mpi.py:
+        # one slab of all time elements, downloaded)
         self.g_vec = np.zeros(self.K.shape[0])
-        for g_t, g_x in data['g']:
+        self.load_plan = slab = None
+        for term in data['g']:
+            if callable(term):
+                if self.load_plan is None:
+                    import torch
+                    from source import _lib
+                    self.load_plan = DeviceLoadPlan(mesh_space, row_order=getattr(M_x, 'stk_row_order', None))
+                    slab = torch.zeros((self.M, self.N_Y), dtype=torch.float64, device=_lib.compute_device())
+                fill_test_space_slab(self.load_plan, mesh_time, term, 0, self.N_Y // 2, slab, accumulate=True)
+                continue
+            g_t, g_x = term
             self.g_vec += np.kron(time_load_test_space(mesh_time, g_t),
                                   space_load(mesh_space, g_x))
+        if slab is not None:
+            self.g_vec += slab.t().contiguous().cpu().numpy().reshape(-1)
         self.u0_x = space_load(mesh_space, data['u0'])
         self.f = self.BT @ (self.K @ self.g_vec) + np.kron(u0_t, self.u0_x)
 
@@ -123,7 +138,8 @@ class HeatEquation:
 
 
 _OPTIONS = (
-    ('problem', str, 'square', 'problem type (square, lshape, cube, square_forced, cube_forced)'),
+    ('problem', str, 'square', 'problem type (square, lshape, cube, square_forced, cube_forced,'
+     ' square_nonseparable, cube_nonseparable, square_moving_source)'),
     ('J_time', int, 5, 'number of time refines'),
     ('J_space', int, 6, 'number of space refines'),
     ('precond', str, 'multigrid', 'spatial preconditioner: multigrid or direct.'),

@@ -402,7 +402,7 @@ class HeatEquationMPI:
             _lib.ptr(u_x), _lib.ptr(self.rhs.buf)))
 
         # -- forcing -- (serial heateq.py:93-102; asserted away in heateq_mpi.py:99)
-        self.g = self.f = self.B = self._BT = self.dofs_test = None
+        self.g = self.f = self.B = self._BT = self.dofs_test = self.load_plan = None
         if data['g']:
             self._set_up_forcing(mesh_time, mesh_space, data['g'])
 
@@ -432,17 +432,20 @@ class HeatEquationMPI:
         plans.set_option('fast_until_cycle', vcycles - 1 if acc['fast_leading_cycles'] else 0)
         plans.set_option('fast_parts', acc['fast_parts'])
 
-    def _set_up_forcing(self, mesh_time, mesh_space, pairs):
-        """g = sum g_t kron g_x on the test-space slab and f = B^T K g + u0_t kron u0_x
-        (reference heateq.py:93-102), with B and B^T on time slabs
+    def _set_up_forcing(self, mesh_time, mesh_space, terms):
+        """g on the test-space slab and f = B^T K g + u0_t kron u0_x (reference
+        heateq.py:93-102).  A term of g is a separable pair (g_t, g_x), g_t kron g_x as
+        the reference has it, or a callable g(t, x, y[, z]) (source/problem.py), whose
+        load is built on the device (assembly.fill_test_space_slab; `load_plan`, None for
+        a problem without a callable).  B and B^T on time slabs
         (mpi_kron.ElementKronMatMPI, on the plan S streams where S has one) and
         K = Minv_Y kron Kinv_x on the driver's own Kinv_x.  In f, Minv_Y is folded into
         the blocks of B^T on the host -- B_k^T Minv_Y is again one 2 x 2 block per
         element, (Minv_Y[e] B_k[e])^T -- so B^T K g = E^T (blocks') (I kron Kinv_x) g is
         one multigrid apply and one element pass; arithmetic='reference' applies K, then
         the plain B^T.  `BT` itself is built when somebody asks for it."""
-        from source.assembly import (element_blocks, time_load_test_space,
-                                     time_matrices_test_space)
+        from source.assembly import (DeviceLoadPlan, element_blocks, fill_test_space_slab,
+                                     time_load_test_space, time_matrices_test_space)
         _, Minv_Y, B1_t, B2_t = time_matrices_test_space(mesh_time)
         b1, b2, minv = element_blocks(B1_t), element_blocks(B2_t), element_blocks(Minv_Y)
         dd = self.dofs_distr
@@ -456,7 +459,17 @@ class HeatEquationMPI:
         self._minv_blocks = _lib.to_dev(minv[dt.e_begin:dt.e_end])
         self.g = KronVectorMPI(dt)
         lib, part = _lib.lib(), None
-        for k, (g_t, g_x) in enumerate(pairs):
+        for k, term in enumerate(terms):
+            if callable(term):
+                # g(t, x) itself, evaluated on the device and summed by libstk's load engine
+                # into this rank's held elements (the copied first one included: the same
+                # instructions on both ranks); the plan is built by the first callable
+                if self.load_plan is None:
+                    self.load_plan = DeviceLoadPlan(mesh_space, row_order=getattr(self.M_x, 'stk_row_order', None))
+                fill_test_space_slab(self.load_plan, mesh_time, term, dt.e_begin, dt.e_end, self.g.buf,
+                                     accumulate=k > 0)
+                continue
+            g_t, g_x = term
             l_t = _lib.to_dev(time_load_test_space(mesh_time, g_t)[dt.t_begin:dt.t_end])
             l_x = _lib.to_dev(space_load(mesh_space, g_x))
             if k and part is None:

@@ -252,6 +252,11 @@ _PROTOTYPES = {
     'stk_p1_result_free': (ctypes.c_int, [c_p]),
     'stk_p1_load_points_2d': (ctypes.c_int, [c_i64, c_i64, c_p, c_p, c_i32, c_p, c_p, c_p]),
     'stk_p1_load_sum_2d': (ctypes.c_int, [c_i64, c_i64, c_p, c_p, c_i32, c_p, c_p, c_p, c_p]),
+    'stk_load_plan_create': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_i32,
+                                            ctypes.POINTER(c_p)]),
+    'stk_load_plan_destroy': (ctypes.c_int, [c_p]),
+    'stk_load_points': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p]),
+    'stk_load_columns': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_i32, c_i32, c_p]),
     'stk_tile_order': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_f64, c_p]),
     'stk_csr_union_count': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_p]),
     'stk_csr_union_fill': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),

@@ -426,6 +426,112 @@ def space_load(mesh, fn, numpy_path=False):
     return vec[free_dofs(mesh)]
 
 
+def simplex_rule(mesh):
+    """(weights, barycentric points) of the degree-4 rule space_load integrates with:
+    Dunavant's 6 points on triangles, Keast's 11 on tetrahedra."""
+    return (_QW, _QL) if mesh.cells.shape[1] == 3 else (_QW3, _QL3)
+
+
+class DeviceLoadPlan:
+    """The load-vector engine of libstk on one mesh (csrc/load_dev.hip, include/stk.h
+    "space-time load vectors"): the mesh and the incidence lists of its free dofs on
+    the device, built once; `points()` = the quadrature points there, computed once;
+    `columns()` = one pair of test-space columns from values at those points.  The sums
+    are those of stk_p1_load_sum_2d, bit for bit.  `row_order`: the mesh-tile order of
+    the free dofs (M_x.stk_row_order), a performance hint.  Not for two streams at once:
+    the plan owns the workspace of `columns()`."""
+    def __init__(self, mesh, max_k=4, row_order=None):
+        import ctypes
+
+        import torch
+
+        from . import _lib
+        self._lib = _lib
+        self.d = mesh.cells.shape[1] - 1
+        self.nc, self.max_k = len(mesh.cells), max_k
+        self.qw, self.ql = (np.ascontiguousarray(a, dtype=np.float64) for a in simplex_rule(mesh))
+        pts = np.ascontiguousarray(mesh.points, dtype=np.float64)
+        cells = np.ascontiguousarray(mesh.cells, dtype=np.int64)
+        fd = np.ascontiguousarray(free_dofs(mesh), dtype=np.int64)
+        self.n_free = len(fd)
+        order = None if row_order is None else np.ascontiguousarray(row_order, dtype=np.int32)
+        assert order is None or order.shape == (self.n_free,)
+        self._plan = ctypes.c_void_p()
+        self._points = None
+        with torch.cuda.device(_lib.compute_device()):
+            _lib.check(_lib.lib().stk_load_plan_create(
+                self.d, mesh.nv, self.nc, pts.ctypes.data, cells.ctypes.data, self.n_free, fd.ctypes.data,
+                None if order is None else order.ctypes.data, max_k, ctypes.byref(self._plan)))
+
+    def __del__(self):
+        if getattr(self, '_plan', None):
+            self._lib.lib().stk_load_plan_destroy(self._plan)
+            self._plan = None
+
+    def points(self, ql=None):
+        """Device tensor (d, nc, nq): coordinate k of quadrature point q of cell t; of
+        the mesh's own rule (kept) or of the barycentric points `ql`."""
+        import torch
+        _lib = self._lib
+        if ql is None and self._points is not None:
+            return self._points
+        rule = self.ql if ql is None else np.ascontiguousarray(ql, dtype=np.float64)
+        assert rule.ndim == 2 and rule.shape[1] == self.d + 1, rule.shape
+        out = torch.empty((self.d, self.nc, rule.shape[0]), dtype=torch.float64, device=_lib.compute_device())
+        _lib.check(_lib.lib().stk_load_points(_lib.stream(), self._plan, rule.shape[0], rule.ctypes.data, _lib.ptr(out)))
+        if ql is None:
+            self._points = out
+        return out
+
+    def columns(self, f, coef, buf, e_local, accumulate=False, qw=None, ql=None):
+        """Columns (2 e_local, 2 e_local + 1) of the slab `buf` (M, ld) (+)= sum_k
+        coef[k][a] L_k, L_k the load vector of f[k] ((n_k, nc, nq) device tensor of values
+        at `points()`)."""
+        import torch
+        _lib = self._lib
+        qw = self.qw if qw is None else np.ascontiguousarray(qw, dtype=np.float64)
+        ql = self.ql if ql is None else np.ascontiguousarray(ql, dtype=np.float64)
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        n_k, nq = coef.shape[0], len(qw)
+        assert coef.shape == (n_k, 2) and ql.shape == (nq, self.d + 1), (coef.shape, ql.shape)
+        assert f.dtype == torch.float64 and f.is_contiguous() and tuple(f.shape) == (n_k, self.nc, nq), tuple(f.shape)
+        M, ld = buf.shape
+        assert M == self.n_free and buf.dtype == torch.float64 and buf.is_contiguous()
+        assert 0 <= e_local and 2 * e_local + 2 <= ld, (e_local, ld)
+        _lib.check(_lib.lib().stk_load_columns(
+            _lib.stream(), self._plan, nq, qw.ctypes.data, ql.ctypes.data, n_k, _lib.ptr(f), coef.ctypes.data,
+            1 if accumulate else 0, ld, _lib.ptr(buf) + 16 * e_local))
+
+
+def time_rule_test_space(mesh_time, nq=4):
+    """(s, coef) of time_load_test_space's rule: the Gauss points s_k on [0, 1] and the
+    coefficients coef[k] = (0.5 h w_k) (1 - s_k, s_k) of the two nodal functions of an
+    element: its load pair is sum_k coef[k] g(h (e + s_k))."""
+    q, w = np.polynomial.legendre.leggauss(nq)
+    s = 0.5 * (q + 1.0)
+    hw = 0.5 * mesh_time.h * w
+    return s, np.stack([hw * (1.0 - s), hw * s], axis=1)
+
+
+def fill_test_space_slab(plan, mesh_time, fn, e_begin, e_end, buf, accumulate=False, nq=4):
+    """int int fn psi_{e,a} phi_i for the time elements [e_begin, e_end), into the columns
+    2 (e - e_begin) + a of the test-space slab `buf` (ElementDistributionMPI: the held
+    elements of a rank), overwritten or added to.  fn(t, x, y[, z]) is a pointwise
+    function of float64 tensors that broadcast, evaluated ON THE DEVICE at the quadrature
+    points of the mesh (plan.points(), computed once) and the `nq` Gauss points
+    t_k = h (e + s_k) of one element at a time -- (nq, cells, points) values, 400 MB on
+    2.1 M triangles; the sums are libstk's (DeviceLoadPlan.columns).  Every element is
+    computed by the same instructions whichever rank holds it."""
+    import torch
+    s, coef = time_rule_test_space(mesh_time, nq)
+    pts = plan.points()
+    shape = (nq,) + tuple(pts.shape[1:])
+    for e in range(e_begin, e_end):
+        t = torch.from_numpy(mesh_time.h * (e + s)).to(pts.device).reshape(nq, 1, 1)
+        f = torch.broadcast_to(torch.as_tensor(fn(t, *pts), dtype=torch.float64, device=pts.device), shape)
+        plan.columns(f.contiguous(), coef, buf, e - e_begin, accumulate=accumulate)
+
+
 def prolongation_matrices(mesh):
     """P_mats[j]: free dofs of level j -> free dofs of level j+1, built from the
     parent-vertex table exactly as reference multigrid.py:39-59:

@@ -15,7 +15,8 @@ from .comm import MPI
 
 # (flag, type, default, help): the options both reference drivers take
 _PROBLEM_OPTIONS = (
-    ('problem', str, 'square', 'problem type (square, lshape, cube, square_forced, cube_forced)'),
+    ('problem', str, 'square', 'problem type (square, lshape, cube, square_forced, cube_forced,'
+     ' square_nonseparable, cube_nonseparable, square_moving_source)'),
     ('J_time', int, 7, 'number of time refines'),
     ('J_space', int, 7, 'number of space refines'),
     ('smoothsteps', int, 3, 'number of smoothing steps'),

@@ -14,7 +14,21 @@ s_kl = sin(k pi x) sin(l pi y),
     cube:    u = exp(-t) s_111 + t s_211, g = (3 pi^2 - 1) exp(-t) s_111 + (1 + 6 pi^2 t) s_211,
 u(0) = s_11 (s_111): two pairs whose space factors differ.  ``data['exact']`` is u
 as a function (t, x, y[, z]) of arrays, for the tests.
+
+An entry of ``data['g']`` may also be a CALLABLE g(t, x, y[, z]): a pointwise function of
+float64 arrays that broadcast, for right-hand sides that are no short separable sum.
+The drivers evaluate it on the device with torch tensors (assembly.fill_test_space_slab;
+it is the user's coefficient function, as u0 is); the functions below take NumPy arrays
+as well, which is what the tests and ``exact`` use.
+``square_nonseparable`` / ``cube_nonseparable``: u = s E with s = sin(pi x) sin(pi y)
+[sin(pi z)] and E = exp(-t (1 + x)), which couples t and x:
+    g = E [(d pi^2 - (1 + x) - t^2) s + 2 t pi cos(pi x) sin(pi y) [sin(pi z)]],  u(0) = s.
+``square_moving_source``: u(0) = 0 and a Gaussian heat source of width 0.1 on a circle,
+    g = exp(-|x - c(t)|^2 / (2 0.1^2)),  c(t) = (0.5 + 0.25 cos 2 pi t, 0.5 + 0.25 sin 2 pi t);
+no exact solution.
 """
+import sys
+
 import numpy as np
 
 from .mesh import (construct_2d_lshape_mesh, construct_2d_square_mesh,
@@ -103,6 +117,65 @@ def cube_forced(J_space, J_time=None):
     return mesh_space, bc, _time_mesh(J_space, J_time), _forced_data(3, _u0_3d, _s211), "cube_forced"
 
 
+def _array_module(*args):
+    """torch if any argument is a torch tensor (subclasses included), else NumPy; torch
+    is not imported for NumPy callers -- a tensor cannot exist before its module."""
+    torch = sys.modules.get('torch')
+    if torch is not None and any(isinstance(a, torch.Tensor) for a in args):
+        return torch
+    return np
+
+
+def _as_array(xp, v):
+    return np.asarray(v, dtype=np.float64) if xp is np else xp.as_tensor(v, dtype=xp.float64)
+
+
+def _nonseparable_data(d):
+    """u = s E on [0,1]^d: u_t = -(1 + x) u, laplace u = E laplace s + 2 grad s . grad E
+    + s laplace E with grad E = (-t E, 0[, 0]) and laplace E = t^2 E."""
+    def parts(t, x):
+        xp = _array_module(t, *x)
+        t, x = _as_array(xp, t), [_as_array(xp, c) for c in x]
+        s, rest = xp.sin(np.pi * x[0]), 1.0  # s in the order of u0's product
+        for c in x[1:]:
+            s, rest = s * xp.sin(np.pi * c), rest * xp.sin(np.pi * c)
+        return xp, t, x[0], s, rest, xp.exp(-t * (1.0 + x[0]))
+
+    def exact(t, *x):
+        xp, t, x0, s, rest, E = parts(t, x)
+        return s * E
+
+    def g(t, *x):
+        xp, t, x0, s, rest, E = parts(t, x)
+        return E * ((d * np.pi**2 - (1.0 + x0) - t * t) * s + 2.0 * t * np.pi * xp.cos(np.pi * x0) * rest)
+
+    return {'g': [g], 'u0': _u0 if d == 2 else _u0_3d, 'exact': exact}
+
+
+def square_nonseparable(J_space, J_time=None):
+    mesh_space, bc = construct_2d_square_mesh(nrefines=J_space)
+    return mesh_space, bc, _time_mesh(J_space, J_time), _nonseparable_data(2), "square_nonseparable"
+
+
+def cube_nonseparable(J_space, J_time=None):
+    mesh_space, bc = construct_3d_cube_mesh(nrefines=J_space)
+    return mesh_space, bc, _time_mesh(J_space, J_time), _nonseparable_data(3), "cube_nonseparable"
+
+
+def _moving_source(t, x, y):
+    xp = _array_module(t, x, y)
+    t, x, y = _as_array(xp, t), _as_array(xp, x), _as_array(xp, y)
+    cx = 0.5 + 0.25 * xp.cos(2.0 * np.pi * t)
+    cy = 0.5 + 0.25 * xp.sin(2.0 * np.pi * t)
+    return xp.exp(-((x - cx)**2 + (y - cy)**2) / (2.0 * 0.1**2))
+
+
+def square_moving_source(J_space, J_time=None):
+    mesh_space, bc = construct_2d_square_mesh(nrefines=J_space)
+    data = {'g': [_moving_source], 'u0': lambda x, y: np.zeros_like(x)}
+    return mesh_space, bc, _time_mesh(J_space, J_time), data, "square_moving_source"
+
+
 def problem_helper(problem, J_space, J_time=None):
     if problem == 'square':
         return square(J_space, J_time)
@@ -116,5 +189,11 @@ def problem_helper(problem, J_space, J_time=None):
         return square_forced(J_space, J_time)
     elif problem == 'cube_forced':
         return cube_forced(J_space, J_time)
+    elif problem == 'square_nonseparable':
+        return square_nonseparable(J_space, J_time)
+    elif problem == 'cube_nonseparable':
+        return cube_nonseparable(J_space, J_time)
+    elif problem == 'square_moving_source':
+        return square_moving_source(J_space, J_time)
     else:
         assert (False)
