@@ -81,7 +81,8 @@ __global__ __launch_bounds__(BS) void elem_time_t_kernel(int64_t total, int32_t 
 #pragma unroll
         for (int k = 0; k < NT; ++k) {
             const double2 *w = reinterpret_cast<const double2 *>(t.z[k]) + i * n_el;
-            if (e_left >= 0) {  // this node is the element's second one: column b = 1
+            // (an element range shorter than the slab: the nodes behind it have no element)
+            if (e_left >= 0 && e_left < n_el) {  // this node is the element's second one: column b = 1
                 const double2 v = w[e_left];
                 const double *b = t.blk[k] + 4 * (int64_t)e_left;
                 acc = fma(b[3], v.y, fma(b[1], v.x, acc));

@@ -227,7 +227,8 @@ __global__ __launch_bounds__(BS, (K >= 12 || RP > 1) ? 4 : 6) void kron_pack_ele
 #pragma unroll
                         for (int k = 0; k < NT; ++k) {
                             const double *w = w0 + k * R * RP * SW;
-                            if (e_left >= 0) {  // this node is the element's second one
+                            // (a range shorter than the slab: the nodes behind it have no element)
+                            if (e_left >= 0 && e_left < a.n_el) {  // this node is the element's second one
                                 const double *b = s_blk + k * 4 * a.n_el + e_left;
                                 acc = fma(b[3 * a.n_el], w[2 * e_left + 1], fma(b[a.n_el], w[2 * e_left], acc));
                             }
