@@ -1093,6 +1093,74 @@ int stk_load_columns(void *stream, const stk_load_plan *plan, int32_t nq,
                      int32_t n_k, const double *f, const double *coef,
                      int32_t accumulate, int32_t ld, double *out_pair);
 
+/* ---- sampling the trial space: u_h(t_k, x_p) on the device ------------------------
+ * The evaluation operator of the trial space (continuous P1 in time on a uniform
+ * mesh, P1 on a simplicial mesh in space): points anywhere in the mesh, times anywhere
+ * in [0, T], read from a slab of nodal values where it lies.  Three steps.
+ *
+ * The PLAN is built once per mesh from the HOST arrays stk_load_plan_create takes:
+ * points [nv][d], cells [nc][d + 1] (d = 2 or 3), free_vertices [n_free] = the vertex
+ * of every slab row.  It uploads the mesh, the map vertex -> slab row (-1 for a
+ * boundary vertex, whose value is 0) and a BUCKET GRID for point location, which
+ * stk_sample_grid_build makes on the host threads of the library (no GPU touched; the
+ * result does not depend on their number): with extent = the longest side of the
+ * bounding box [lo, hi] and widen = 1e-12 extent, the box [lo - widen, hi + widen] is
+ * cut into bins[k] = round(nc^(1/d)) equal bins per axis,
+ *     bin of x along k = floor((x - (lo[k] - widen)) * inv_width[k]), clamped to
+ *                        0 .. bins[k] - 1;    bin index = (iz bins[1] + iy) bins[0] + ix,
+ * and every cell is listed, in ascending cell order, in every bin between the bins of
+ * the two corners of its bounding box widened by `widen`.  Nothing assumes nested or
+ * congruent cells.  _sizes reports bins [3], the shifted corner lo [3], inv_width [3]
+ * (axes beyond d: 1, 0, 0), widen and the number of list entries; _copy writes
+ * bin_ptr [bins + 1] and bin_cells [entries] (CSR).
+ *
+ * stk_sample_locate takes DEVICE coordinates x [d][n_p] and writes cell [n_p] (int32,
+ * -1 = outside the mesh) and lam [n_p][d + 1].  One lane per point; the candidates are
+ * the cells of the point's bin (a point outside the box falls into an edge bin).
+ * Barycentric coordinates of a candidate with vertices p0 .. pd, e_r = p_r - p0,
+ * q = x - p0: triangles l1 = (q x e2) / (e1 x e2), l2 = (e1 x q) / (e1 x e2) with
+ * a x b = a0 b1 - a1 b0; tetrahedra l1 = q . (e2 x e3) / det, l2 = q . (e3 x e1) / det,
+ * l3 = q . (e1 x e2) / det, det = e1 . (e2 x e3), dot products summed from the left;
+ * l0 = ((1 - l1) - l2) [- l3].  No fused multiply-adds.  The chosen cell has the largest
+ * min_a l_a, the lowest index among equals; the point is inside iff that minimum is
+ * >= -1e-12.  lam holds the chosen candidate's coordinates also for an outside point
+ * (NaN if its bin is empty).
+ *
+ * stk_sample_eval takes the located points, a slab (M = n_free rows, n_loc valid
+ * columns, leading dimension ld) and n_k requests as HOST arrays columns [n_k][2]
+ * (local columns c0, c1 of the slab; -1 = "not on this rank") and weights [n_k][2],
+ * and writes the DEVICE array out [n_k][ld_out >= n_p] (64-bit addressing):
+ *     out[k][p] = p0 + p1,   p_a = w_a (((l0 u[v0][c_a] + l1 u[v1][c_a]) + l2 u[v2][c_a])
+ *                                       [+ l3 u[v3][c_a]]),
+ * v_a the slab rows of the cell's vertices; every product and every sum is rounded on
+ * its own; a boundary vertex contributes the value 0; a term whose column is -1 is
+ * exactly 0.0 and its rows are not read; an outside point gives NaN.  Only the named
+ * columns are read (never the padding of an odd n_loc).  With the two columns of a
+ * request owned by different ranks, each rank's out holds one of the two terms and 0.0
+ * for the other: their sum over the ranks is the one-rank double.  Requests are served in
+ * launches of at most 96 distinct columns each (one launch for a slab of up to 96 time
+ * steps, whatever n_k).  The plan owns the request tables of a call in flight: one plan
+ * serves one stream at a time.  No atomics. */
+typedef struct stk_sample_grid stk_sample_grid;
+typedef struct stk_sample_plan stk_sample_plan;
+int stk_sample_grid_build(int32_t d, int64_t nv, int64_t nc, const double *points,
+                          const int64_t *cells, stk_sample_grid **out);
+int stk_sample_grid_sizes(const stk_sample_grid *grid, int32_t *bins, double *lo,
+                          double *inv_width, double *widen, int64_t *n_entries);
+int stk_sample_grid_copy(const stk_sample_grid *grid, int32_t *bin_ptr,
+                         int32_t *bin_cells);
+int stk_sample_grid_free(stk_sample_grid *grid);
+int stk_sample_plan_create(int32_t d, int64_t nv, int64_t nc, const double *points,
+                           const int64_t *cells, int64_t n_free,
+                           const int64_t *free_vertices, stk_sample_plan **out);
+int stk_sample_plan_destroy(stk_sample_plan *plan);
+int stk_sample_locate(void *stream, const stk_sample_plan *plan, int64_t n_p,
+                      const double *x, int32_t *cell, double *lam);
+int stk_sample_eval(void *stream, stk_sample_plan *plan, int64_t n_p,
+                    const int32_t *cell, const double *lam, int32_t M, int32_t n_loc,
+                    int32_t ld, const double *slab, int32_t n_k, const int32_t *columns,
+                    const double *weights, int64_t ld_out, double *out);
+
 /* ---- plan construction on the host threads: processing order and union pattern ---
  * stk_tile_order: the mesh-tile order of n dofs with coordinates coords [n][d]
  * (d = 2 or 3): the bounding box cut into cubes of edge `side` from the corner `lo`

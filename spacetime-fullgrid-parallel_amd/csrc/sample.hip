@@ -1,0 +1,587 @@
+// The evaluation operator of the trial space (include/stk.h "sampling the trial space"):
+// u_h(t_k, x_p) of a slab of nodal values for arbitrary points of a simplicial P1 mesh
+// and arbitrary times -- rasters, probes and line cuts without downloading the slab.
+//
+//  * stk_sample_grid_build  HOST: a uniform bucket grid over the bounding box, every cell
+//                           listed (CSR, ascending) in every bin its widened box touches.
+//                           On the host threads of the library; no GPU touched.
+//  * stk_sample_plan_create uploads the mesh, the vertex -> slab-row map and that grid
+//  * stk_sample_locate      one lane per point: the cells of the point's bin, barycentric
+//                           coordinates by the signed-area / cofactor expressions, the
+//                           cell with the largest smallest coordinate
+//  * stk_sample_eval        out[k][p] = w0 s_p(c0) + w1 s_p(c1) with the spatial sums
+//                           s_p(c) = ((l0 u[v0][c] + l1 u[v1][c]) + l2 u[v2][c]) [+ ...]
+//
+// THE EVAL KERNEL.  A slab row is contiguous in time and a point needs d + 1 whole rows, so
+// the pass is a row gather, and its output is time-major: points x times turned through
+// LDS.  A workgroup takes 64 consecutive points.  Pass 1 walks (point, needed column) with
+// the column on neighbouring lanes -- a wavefront reads its rows in whole lines, every
+// needed entry of a row once per call -- and leaves s_p(c) in an LDS tile
+// [point][column] (odd row length: pass 2's column reads are conflict-free).  Pass 2
+// walks (request, point) with the point on neighbouring lanes: a wavefront is one request,
+// reads its two columns of the tile and stores 512 contiguous bytes of out.  The spatial
+// sum does not depend on the request, so it is formed once per column however many
+// requests read it.  No atomics; every sum has one owner and one order.
+//
+// ARITHMETIC: every product and every sum rounded on its own -- contraction is SWITCHED
+// OFF for this file (the pragma below and -ffp-contract=off in the Makefile), as for the
+// load engine, and no kernel here calls fma.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <thread>
+#include <vector>
+
+#include "stk_common.h"
+
+#pragma clang fp contract(off)
+
+struct stk_sample_grid {
+    int32_t d;
+    int32_t nb[3];
+    double lo[3], inv_w[3];  // bin of x along k: floor((x - lo[k]) * inv_w[k]), clamped
+    double widen;
+    std::vector<int32_t> bin_ptr, bin_cells;
+};
+
+namespace {
+
+constexpr int BS = 256;
+constexpr int TP = 64;         // points of an eval tile = one wavefront of pass 2
+constexpr int UNROLL = 4;      // steps of pass 1 whose loads are in flight together
+constexpr int MAX_COLS = 96;   // distinct columns of one launch: the tile stays below 50 KB
+constexpr double INSIDE = -1e-12;
+
+struct grid_desc {
+    int32_t nb[3];
+    double lo[3], inv_w[3];
+};
+
+// The bin of a coordinate: the SAME expression files the cells (host) and looks the points
+// up (device); it is monotone in x, so a point between two corners of a box lands between
+// their bins whatever the rounding.
+__host__ __device__ inline int32_t bin_of(double x, double lo, double inv_w, int32_t nb)
+{
+    const double t = floor((x - lo) * inv_w);
+    if (!(t >= 0.0)) return 0;  // below the box, or not a number
+    if (t >= (double)nb) return nb - 1;
+    return (int32_t)t;
+}
+
+int host_threads(int64_t items)
+{
+    int T = (int)std::thread::hardware_concurrency();
+    if (const char *env = getenv("STK_HOST_THREADS")) T = atoi(env);
+    T = std::max(1, std::min(T, 32));
+    if (items < 16384) T = 1;
+    return T;
+}
+
+template <class F>
+void on_threads(int T, F body)
+{
+    if (T == 1) {
+        body(0);
+        return;
+    }
+    std::vector<std::thread> pool;
+    for (int k = 0; k < T; ++k) pool.emplace_back(body, k);
+    for (auto &th : pool) th.join();
+}
+
+inline int64_t share(int64_t n, int T, int k) { return n * k / T; }
+
+int check_mesh(const char *who, int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells)
+{
+    STK_REQUIRE((d == 2 || d == 3) && nv > 0 && nc > 0 && points && cells, "%s: bad arguments", who);
+    STK_REQUIRE(nv < ((int64_t)1 << 31) && (int64_t)(d + 1) * nc < ((int64_t)1 << 31), "%s: mesh too large for 32-bit tables",
+                who);
+    for (int64_t q = 0; q < (int64_t)(d + 1) * nc; ++q)
+        STK_REQUIRE(cells[q] >= 0 && cells[q] < nv, "%s: cell %lld names vertex %lld", who, (long long)(q / (d + 1)),
+                    (long long)cells[q]);
+    return 0;
+}
+
+// ---- barycentric coordinates -----------------------------------------------------------
+// triangles: signed areas over the signed area of the cell; tetrahedra: the cofactors of
+// the edge matrix (cross products) over its determinant, every dot product summed from the
+// left; l0 = ((1 - l1) - l2) [- l3].  A vertex of the cell gets exactly (1, 0, 0) there.
+template <int D>
+__device__ inline void barycentric(const double *__restrict__ pts, const int32_t *__restrict__ c, const double *x,
+                                   double *l)
+{
+    const double *p0 = pts + D * (int64_t)c[0];
+    double e[D][D], q[D];
+#pragma unroll
+    for (int r = 0; r < D; ++r)
+#pragma unroll
+        for (int k = 0; k < D; ++k) e[r][k] = pts[D * (int64_t)c[r + 1] + k] - p0[k];
+#pragma unroll
+    for (int k = 0; k < D; ++k) q[k] = x[k] - p0[k];
+    if constexpr (D == 2) {
+        const double det = e[0][0] * e[1][1] - e[0][1] * e[1][0];
+        l[1] = (q[0] * e[1][1] - q[1] * e[1][0]) / det;
+        l[2] = (e[0][0] * q[1] - e[0][1] * q[0]) / det;
+        l[0] = (1.0 - l[1]) - l[2];
+    } else {
+        double n[3][3];  // n[0] = e1 x e2, n[1] = e2 x e0, n[2] = e0 x e1
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double *a = e[(r + 1) % 3], *b = e[(r + 2) % 3];
+            n[r][0] = a[1] * b[2] - a[2] * b[1];
+            n[r][1] = a[2] * b[0] - a[0] * b[2];
+            n[r][2] = a[0] * b[1] - a[1] * b[0];
+        }
+        const double det = (e[0][0] * n[0][0] + e[0][1] * n[0][1]) + e[0][2] * n[0][2];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) l[r + 1] = ((q[0] * n[r][0] + q[1] * n[r][1]) + q[2] * n[r][2]) / det;
+        l[0] = ((1.0 - l[1]) - l[2]) - l[3];
+    }
+}
+
+// one lane per point
+template <int D>
+__global__ __launch_bounds__(BS) void sample_locate_kernel(int64_t n_p, const double *__restrict__ x, grid_desc g,
+                                                           const int32_t *__restrict__ bin_ptr,
+                                                           const int32_t *__restrict__ bin_cells,
+                                                           const double *__restrict__ pts,
+                                                           const int32_t *__restrict__ cells, int32_t *__restrict__ cell_out,
+                                                           double *__restrict__ lam_out)
+{
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    for (int64_t p = (int64_t)blockIdx.x * BS + threadIdx.x; p < n_p; p += stride) {
+        double xp[D];
+        int64_t bin = 0;
+#pragma unroll
+        for (int k = D - 1; k >= 0; --k) {
+            xp[k] = x[k * n_p + p];
+            bin = bin * g.nb[k] + bin_of(xp[k], g.lo[k], g.inv_w[k], g.nb[k]);
+        }
+        const double nan = __builtin_nan("");
+        double best = -__builtin_inf(), lb[D + 1];
+        int32_t cb = -1;
+#pragma unroll
+        for (int a = 0; a <= D; ++a) lb[a] = nan;
+        const int32_t begin = bin_ptr[bin], end = bin_ptr[bin + 1];
+        for (int32_t s = begin; s < end; ++s) {  // ascending cells: `>` keeps the lowest on a tie
+            const int32_t t = bin_cells[s];
+            double l[D + 1];
+            barycentric<D>(pts, cells + (D + 1) * (int64_t)t, xp, l);
+            double m = l[0];
+#pragma unroll
+            for (int a = 1; a <= D; ++a) m = l[a] < m ? l[a] : m;
+            bool any_nan = false;
+#pragma unroll
+            for (int a = 0; a <= D; ++a) any_nan = any_nan || l[a] != l[a];
+            if (!any_nan && m > best) {
+                best = m, cb = t;
+#pragma unroll
+                for (int a = 0; a <= D; ++a) lb[a] = l[a];
+            }
+        }
+        cell_out[p] = best >= INSIDE ? cb : -1;
+#pragma unroll
+        for (int a = 0; a <= D; ++a) lam_out[(D + 1) * p + a] = lb[a];
+    }
+}
+
+// LDS of the eval kernel: the tile [TP][stride] of spatial sums, then per point its
+// coordinates [TP][D + 1] and slab rows [TP][D + 1] (-1 = boundary vertex, -2 = outside)
+template <int D>
+__global__ __launch_bounds__(BS) void sample_eval_kernel(int64_t n_p, int64_t nc, const int32_t *__restrict__ cell,
+                                                         const double *__restrict__ lam,
+                                                         const int32_t *__restrict__ cells,
+                                                         const int32_t *__restrict__ row_of, int32_t ld,
+                                                         const double *__restrict__ u, int32_t n_c,
+                                                         const int32_t *__restrict__ cols, int32_t n_k,
+                                                         const int32_t *__restrict__ req_col,
+                                                         const double *__restrict__ req_w, int64_t ld_out,
+                                                         double *__restrict__ out)
+{
+    extern __shared__ double lds[];
+    const int stride = n_c | 1;
+    double *tile = lds;
+    double *pl = lds + TP * stride;
+    int32_t *pr = reinterpret_cast<int32_t *>(pl + TP * (D + 1));
+    const int tid = threadIdx.x;
+    const int64_t n_tiles = (n_p + TP - 1) / TP;
+    for (int64_t tile_id = blockIdx.x; tile_id < n_tiles; tile_id += gridDim.x) {
+        const int64_t p0 = tile_id * TP;
+        const int here = (int)(n_p - p0 < TP ? n_p - p0 : TP);
+        if (tid < here) {
+            const int32_t t = cell[p0 + tid];
+#pragma unroll
+            for (int a = 0; a <= D; ++a) {
+                pl[tid * (D + 1) + a] = lam[(D + 1) * (p0 + tid) + a];
+                pr[tid * (D + 1) + a] = t < 0 || t >= nc ? -2 : row_of[cells[(D + 1) * (int64_t)t + a]];
+            }
+        }
+        __syncthreads();
+        // pass 1: (point, column), the column on neighbouring lanes; the loads of UNROLL
+        // steps are issued before the first sum needs one (a step alone waits out a whole
+        // memory round trip per (d + 1) loads)
+        const int total = here * n_c;
+        for (int base = tid; base < total; base += BS * UNROLL) {
+            double v[UNROLL][D + 1], l[UNROLL][D + 1];
+            int at[UNROLL];
+#pragma unroll
+            for (int s = 0; s < UNROLL; ++s) {
+                const int idx = base + s * BS;
+                at[s] = -1;
+                if (idx < total) {
+                    const int p = idx / n_c, j = idx - p * n_c;
+                    if (pr[p * (D + 1)] != -2) {
+                        at[s] = p * stride + j;
+                        const int32_t c = cols[j];
+#pragma unroll
+                        for (int a = 0; a <= D; ++a) {
+                            const int32_t r = pr[p * (D + 1) + a];
+                            l[s][a] = pl[p * (D + 1) + a];
+                            v[s][a] = r >= 0 ? u[(int64_t)r * ld + c] : 0.0;
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < UNROLL; ++s) {
+                if (at[s] < 0) continue;
+                double sum = l[s][0] * v[s][0];
+#pragma unroll
+                for (int a = 1; a <= D; ++a) sum = sum + l[s][a] * v[s][a];
+                tile[at[s]] = sum;
+            }
+        }
+        __syncthreads();
+        // pass 2: (request, point), the point on neighbouring lanes
+        for (int idx = tid; idx < n_k * TP; idx += BS) {
+            const int k = idx / TP, p = idx % TP;
+            if (p >= here) continue;
+            double v;
+            if (pr[p * (D + 1)] == -2) {
+                v = __builtin_nan("");
+            } else {
+                const int32_t j0 = req_col[2 * k], j1 = req_col[2 * k + 1];
+                const double a0 = j0 >= 0 ? req_w[2 * k] * tile[p * stride + j0] : 0.0;
+                const double a1 = j1 >= 0 ? req_w[2 * k + 1] * tile[p * stride + j1] : 0.0;
+                v = a0 + a1;
+            }
+            out[(int64_t)k * ld_out + p0 + p] = v;
+        }
+        __syncthreads();
+    }
+}
+
+template <typename T>
+int upload(T **dst, const T *src, size_t n)
+{
+    STK_HIP(hipMalloc((void **)dst, (n ? n : 1) * sizeof(T)));
+    if (n) STK_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+}  // namespace
+
+struct stk_sample_plan {
+    int32_t d;
+    int64_t nv, nc, n_free;
+    grid_desc g;
+    double *points;      // [nv][d]
+    int32_t *cells;      // [nc][d + 1]
+    int32_t *row_of;     // [nv]: slab row of a vertex, -1 on the boundary
+    int32_t *bin_ptr;    // [bins + 1]
+    int32_t *bin_cells;  // cells of bin b: bin_ptr[b] .. bin_ptr[b + 1], ascending
+    // request tables of stk_sample_eval: written into pinned host memory, copied on the
+    // caller's stream; `copied` guards the host side against the next call
+    char *req_host, *req_dev;
+    size_t req_bytes;
+    hipEvent_t copied;
+    bool copy_pending;
+};
+
+namespace {
+
+void release(stk_sample_plan *p)
+{
+    if (!p) return;
+    void *arrays[] = {p->points, p->cells, p->row_of, p->bin_ptr, p->bin_cells, p->req_dev};
+    for (void *a : arrays)
+        if (a) (void)hipFree(a);
+    if (p->req_host) (void)hipHostFree(p->req_host);
+    if (p->copied) (void)hipEventDestroy(p->copied);
+    delete p;
+}
+
+}  // namespace
+
+extern "C" int stk_sample_grid_build(int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells,
+                                     stk_sample_grid **out)
+{
+    STK_REQUIRE(out, "stk_sample_grid_build: null pointer");
+    if (int rc = check_mesh("stk_sample_grid_build", d, nv, nc, points, cells)) return rc;
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    for (int k = 0; k < d; ++k) lo[k] = hi[k] = points[k];
+    for (int64_t v = 0; v < nv; ++v)
+        for (int k = 0; k < d; ++k) {
+            const double x = points[d * v + k];
+            STK_REQUIRE(std::isfinite(x), "stk_sample_grid_build: vertex %lld is not finite", (long long)v);
+            lo[k] = std::min(lo[k], x), hi[k] = std::max(hi[k], x);
+        }
+    double extent = 0.0;
+    for (int k = 0; k < d; ++k) extent = std::max(extent, hi[k] - lo[k]);
+    STK_REQUIRE(extent > 0.0, "stk_sample_grid_build: the mesh has no extent");
+    stk_sample_grid *g = new stk_sample_grid();
+    g->d = d, g->widen = 1e-12 * extent;
+    const int32_t nb = (int32_t)std::max(1.0, std::floor(std::pow((double)nc, 1.0 / d) + 0.5));
+    int64_t n_bins = 1;
+    for (int k = 0; k < 3; ++k) {
+        g->nb[k] = k < d ? nb : 1;
+        g->lo[k] = k < d ? lo[k] - g->widen : 0.0;
+        g->inv_w[k] = k < d ? (double)nb / ((hi[k] - lo[k]) + 2.0 * g->widen) : 0.0;
+        n_bins *= g->nb[k];
+    }
+    if (n_bins >= ((int64_t)1 << 31)) {
+        delete g;
+        stk_set_error("stk_sample_grid_build: too many bins for 32-bit tables");
+        return 2;
+    }
+    // pass 1, over the cells: the bins each widened box reaches, per axis
+    std::vector<int32_t> range((size_t)nc * 6);
+    const int T = host_threads(nc);
+    on_threads(T, [&](int k) {
+        for (int64_t t = share(nc, T, k); t < share(nc, T, k + 1); ++t) {
+            int32_t *r = &range[(size_t)t * 6];
+            for (int a = 0; a < 3; ++a) r[2 * a] = r[2 * a + 1] = 0;
+            for (int a = 0; a < d; ++a) {
+                double bl = points[d * cells[(d + 1) * t] + a], bh = bl;
+                for (int j = 1; j <= d; ++j) {
+                    const double x = points[d * cells[(d + 1) * t + j] + a];
+                    bl = std::min(bl, x), bh = std::max(bh, x);
+                }
+                r[2 * a] = bin_of(bl - g->widen, g->lo[a], g->inv_w[a], g->nb[a]);
+                r[2 * a + 1] = bin_of(bh + g->widen, g->lo[a], g->inv_w[a], g->nb[a]);
+            }
+        }
+    });
+    // passes 2 and 3, over slabs of bins along the last axis: every thread counts, then
+    // files, the cells of ITS bins in ascending cell order -- one owner per list, the
+    // result does not depend on the number of threads
+    const int last = d - 1;
+    const int TB = std::min<int>(T, g->nb[last]);
+    g->bin_ptr.assign((size_t)n_bins + 1, 0);
+    auto for_bins = [&](int k, auto &&visit) {
+        const int32_t s0 = (int32_t)share(g->nb[last], TB, k), s1 = (int32_t)share(g->nb[last], TB, k + 1);
+        for (int64_t t = 0; t < nc; ++t) {
+            int32_t r[6];
+            for (int a = 0; a < 6; ++a) r[a] = range[(size_t)t * 6 + a];
+            r[2 * last] = std::max(r[2 * last], s0), r[2 * last + 1] = std::min(r[2 * last + 1], s1 - 1);
+            for (int32_t iz = r[4]; iz <= r[5]; ++iz)
+                for (int32_t iy = r[2]; iy <= r[3]; ++iy)
+                    for (int32_t ix = r[0]; ix <= r[1]; ++ix)
+                        visit(((int64_t)iz * g->nb[1] + iy) * g->nb[0] + ix, (int32_t)t);
+        }
+    };
+    on_threads(TB, [&](int k) { for_bins(k, [&](int64_t b, int32_t) { ++g->bin_ptr[(size_t)b + 1]; }); });
+    int64_t total = 0;
+    for (int64_t b = 0; b < n_bins; ++b) {
+        total += g->bin_ptr[(size_t)b + 1];
+        if (total >= ((int64_t)1 << 31)) {
+            delete g;
+            stk_set_error("stk_sample_grid_build: bin lists too large for 32-bit tables");
+            return 2;
+        }
+        g->bin_ptr[(size_t)b + 1] = (int32_t)total;
+    }
+    g->bin_cells.resize((size_t)total);
+    std::vector<int32_t> cursor(g->bin_ptr.begin(), g->bin_ptr.end() - 1);
+    on_threads(TB, [&](int k) { for_bins(k, [&](int64_t b, int32_t t) { g->bin_cells[(size_t)cursor[(size_t)b]++] = t; }); });
+    *out = g;
+    return 0;
+}
+
+extern "C" int stk_sample_grid_sizes(const stk_sample_grid *grid, int32_t *bins, double *lo, double *inv_width,
+                                     double *widen, int64_t *n_entries)
+{
+    STK_REQUIRE(grid, "stk_sample_grid_sizes: null pointer");
+    for (int k = 0; k < 3; ++k) {
+        if (bins) bins[k] = grid->nb[k];
+        if (lo) lo[k] = grid->lo[k];
+        if (inv_width) inv_width[k] = grid->inv_w[k];
+    }
+    if (widen) *widen = grid->widen;
+    if (n_entries) *n_entries = (int64_t)grid->bin_cells.size();
+    return 0;
+}
+
+extern "C" int stk_sample_grid_copy(const stk_sample_grid *grid, int32_t *bin_ptr, int32_t *bin_cells)
+{
+    STK_REQUIRE(grid && bin_ptr && bin_cells, "stk_sample_grid_copy: null pointer");
+    std::copy(grid->bin_ptr.begin(), grid->bin_ptr.end(), bin_ptr);
+    std::copy(grid->bin_cells.begin(), grid->bin_cells.end(), bin_cells);
+    return 0;
+}
+
+extern "C" int stk_sample_grid_free(stk_sample_grid *grid)
+{
+    delete grid;
+    return 0;
+}
+
+extern "C" int stk_sample_plan_create(int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells,
+                                      int64_t n_free, const int64_t *free_vertices, stk_sample_plan **out)
+{
+    STK_REQUIRE(out && n_free > 0 && free_vertices, "stk_sample_plan_create: bad arguments");
+    stk_sample_grid *grid = nullptr;
+    if (int rc = stk_sample_grid_build(d, nv, nc, points, cells, &grid)) return rc;
+    std::vector<int32_t> row_of((size_t)nv, -1);
+    for (int64_t i = 0; i < n_free; ++i) {
+        const int64_t v = free_vertices[i];
+        if (!(v >= 0 && v < nv && row_of[(size_t)v] < 0 && n_free < ((int64_t)1 << 31))) {
+            stk_sample_grid_free(grid);
+            stk_set_error("stk_sample_plan_create: free dof %lld is vertex %lld (out of range or named twice)", (long long)i,
+                          (long long)v);
+            return 2;
+        }
+        row_of[(size_t)v] = (int32_t)i;
+    }
+    std::vector<int32_t> cells32((size_t)(d + 1) * nc);
+    for (size_t q = 0; q < cells32.size(); ++q) cells32[q] = (int32_t)cells[q];
+
+    stk_sample_plan *p = new stk_sample_plan();
+    p->d = d, p->nv = nv, p->nc = nc, p->n_free = n_free;
+    for (int k = 0; k < 3; ++k) p->g.nb[k] = grid->nb[k], p->g.lo[k] = grid->lo[k], p->g.inv_w[k] = grid->inv_w[k];
+    int rc = upload(&p->points, points, (size_t)nv * d);
+    if (!rc) rc = upload(&p->cells, cells32.data(), cells32.size());
+    if (!rc) rc = upload(&p->row_of, row_of.data(), row_of.size());
+    if (!rc) rc = upload(&p->bin_ptr, grid->bin_ptr.data(), grid->bin_ptr.size());
+    if (!rc) rc = upload(&p->bin_cells, grid->bin_cells.data(), grid->bin_cells.size());
+    stk_sample_grid_free(grid);
+    if (!rc && hipEventCreateWithFlags(&p->copied, hipEventDisableTiming) != hipSuccess) {
+        stk_set_error("stk_sample_plan_create: no event");
+        rc = 1;
+    }
+    if (rc) {
+        release(p);
+        return rc;
+    }
+    *out = p;
+    return 0;
+}
+
+extern "C" int stk_sample_plan_destroy(stk_sample_plan *plan)
+{
+    release(plan);
+    return 0;
+}
+
+extern "C" int stk_sample_locate(void *stream, const stk_sample_plan *plan, int64_t n_p, const double *x, int32_t *cell,
+                                 double *lam)
+{
+    const stk_timed timed_(STK_OP_SPACE, stream);
+    STK_REQUIRE(plan && n_p >= 0 && (n_p == 0 || (x && cell && lam)), "stk_sample_locate: bad arguments");
+    if (n_p == 0) return 0;
+    const dim3 grid(stk_flat_grid(n_p, BS));
+    hipStream_t st = stk_stream(stream);
+    if (plan->d == 2)
+        hipLaunchKernelGGL(sample_locate_kernel<2>, grid, dim3(BS), 0, st, n_p, x, plan->g, plan->bin_ptr, plan->bin_cells,
+                           plan->points, plan->cells, cell, lam);
+    else
+        hipLaunchKernelGGL(sample_locate_kernel<3>, grid, dim3(BS), 0, st, n_p, x, plan->g, plan->bin_ptr, plan->bin_cells,
+                           plan->points, plan->cells, cell, lam);
+    STK_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int stk_sample_eval(void *stream, stk_sample_plan *plan, int64_t n_p, const int32_t *cell, const double *lam,
+                               int32_t M, int32_t n_loc, int32_t ld, const double *slab, int32_t n_k, const int32_t *columns,
+                               const double *weights, int64_t ld_out, double *out)
+{
+    const stk_timed timed_(STK_OP_SPACE, stream);
+    STK_REQUIRE(plan && n_p >= 0 && n_k >= 0, "stk_sample_eval: bad arguments");
+    if (n_p == 0 || n_k == 0) return 0;
+    STK_REQUIRE(cell && lam && slab && columns && weights && out, "stk_sample_eval: null pointer");
+    STK_REQUIRE(M == plan->n_free, "stk_sample_eval: a slab of %d rows on a plan of %lld free dofs", M,
+                (long long)plan->n_free);
+    STK_REQUIRE(n_loc >= 1 && ld >= n_loc && ld_out >= n_p, "stk_sample_eval: n_loc=%d ld=%d ld_out=%lld n_p=%lld", n_loc, ld,
+                (long long)ld_out, (long long)n_p);
+    for (int k = 0; k < 2 * n_k; ++k)
+        STK_REQUIRE(columns[k] >= -1 && columns[k] < n_loc, "stk_sample_eval: request %d names column %d of %d", k / 2,
+                    columns[k], n_loc);
+    // launches: consecutive requests whose distinct columns fit one tile.  Per launch
+    // [n_c columns | n_kc x 2 indices into them (int32) | pad to 8 | n_kc x 2 weights]
+    struct launch {
+        int32_t k0, n_kc, n_c;
+        size_t off_cols, off_req, off_w;
+    };
+    std::vector<launch> launches;
+    std::vector<int32_t> slot((size_t)n_loc, -1), used;
+    size_t bytes = 0;
+    std::vector<char> image;
+    auto flush = [&](int32_t k0, int32_t k1) {
+        launch L;
+        L.k0 = k0, L.n_kc = k1 - k0, L.n_c = (int32_t)used.size();  // 0: all "not on this rank"
+        std::vector<int32_t> head(used);
+        for (int32_t k = k0; k < k1; ++k)
+            for (int a = 0; a < 2; ++a) head.push_back(columns[2 * k + a] < 0 ? -1 : slot[(size_t)columns[2 * k + a]]);
+        if (head.size() & 1) head.push_back(0);
+        L.off_cols = bytes, L.off_req = bytes + 4 * (size_t)L.n_c;
+        L.off_w = bytes + 4 * head.size();
+        image.resize(L.off_w + 16 * (size_t)L.n_kc);
+        std::copy((const char *)head.data(), (const char *)(head.data() + head.size()), image.begin() + L.off_cols);
+        std::copy((const char *)(weights + 2 * k0), (const char *)(weights + 2 * k1), image.begin() + L.off_w);
+        bytes = image.size();
+        launches.push_back(L);
+        for (int32_t c : used) slot[(size_t)c] = -1;
+        used.clear();
+    };
+    int32_t k0 = 0;
+    for (int32_t k = 0; k < n_k; ++k) {
+        int fresh = 0;
+        for (int a = 0; a < 2; ++a) {
+            const int32_t c = columns[2 * k + a];
+            fresh += c >= 0 && slot[(size_t)c] < 0 && !(a == 1 && c == columns[2 * k]);
+        }
+        if ((int)used.size() + fresh > MAX_COLS) flush(k0, k), k0 = k;
+        for (int a = 0; a < 2; ++a) {
+            const int32_t c = columns[2 * k + a];
+            if (c >= 0 && slot[(size_t)c] < 0) slot[(size_t)c] = (int32_t)used.size(), used.push_back(c);
+        }
+    }
+    flush(k0, n_k);
+
+    hipStream_t st = stk_stream(stream);
+    if (plan->copy_pending) STK_HIP(hipEventSynchronize(plan->copied));  // the host image is free again
+    if (bytes > plan->req_bytes) {
+        // the device image may still be read by an earlier call's kernels
+        STK_HIP(hipStreamSynchronize(st));
+        if (plan->req_dev) (void)hipFree(plan->req_dev);
+        if (plan->req_host) (void)hipHostFree(plan->req_host);
+        plan->req_dev = plan->req_host = nullptr, plan->req_bytes = 0;
+        const size_t room = std::max<size_t>(2 * bytes, 4096);
+        STK_HIP(hipMalloc((void **)&plan->req_dev, room));
+        STK_HIP(hipHostMalloc((void **)&plan->req_host, room, hipHostMallocDefault));
+        plan->req_bytes = room;
+    }
+    std::copy(image.begin(), image.end(), plan->req_host);
+    STK_HIP(hipMemcpyAsync(plan->req_dev, plan->req_host, bytes, hipMemcpyHostToDevice, st));
+    STK_HIP(hipEventRecord(plan->copied, st));
+    plan->copy_pending = true;
+
+    const int d = plan->d;
+    const int64_t n_tiles = (n_p + TP - 1) / TP;
+    const dim3 grid((unsigned)std::min<int64_t>(n_tiles, 256 * 16));
+    for (const launch &L : launches) {
+        const size_t lds = (size_t)TP * (L.n_c | 1) * sizeof(double) + (size_t)TP * (d + 1) * (sizeof(double) + sizeof(int32_t));
+        const int32_t *cols = (const int32_t *)(plan->req_dev + L.off_cols);
+        const int32_t *req = (const int32_t *)(plan->req_dev + L.off_req);
+        const double *w = (const double *)(plan->req_dev + L.off_w);
+        double *o = out + (int64_t)L.k0 * ld_out;
+        if (d == 2)
+            hipLaunchKernelGGL(sample_eval_kernel<2>, grid, dim3(BS), lds, st, n_p, plan->nc, cell, lam, plan->cells, plan->row_of, ld,
+                               slab, L.n_c, cols, L.n_kc, req, w, ld_out, o);
+        else
+            hipLaunchKernelGGL(sample_eval_kernel<3>, grid, dim3(BS), lds, st, n_p, plan->nc, cell, lam, plan->cells, plan->row_of, ld,
+                               slab, L.n_c, cols, L.n_kc, req, w, ld_out, o);
+        STK_LAUNCH_CHECK();
+    }
+    return 0;
+}

@@ -19,6 +19,7 @@ import numpy as np
 import scipy.sparse as sp
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from source import driver  # noqa: E402
 from source.assembly import (DeviceLoadPlan, fill_test_space_slab,  # noqa: E402
                              space_load, space_matrices,
                              time_load_test_space, time_matrices,
@@ -42,6 +43,8 @@ class HeatEquation:
         mesh_space, bc, mesh_time, data, fn = problem_helper(problem,
                                                              J_space=J_space,
                                                              J_time=J_time)
+        # what sample() builds its plan from, on first use
+        self._sample_meshes, self.sample_plan = (mesh_space, mesh_time), None
         A_t, L_t, M_t, G_t, u0_t = time_matrices(mesh_time)
         M_Y, Minv_Y, B1_t, B2_t = time_matrices_test_space(mesh_time)
         M_x, A_x = space_matrices(mesh_space)
@@ -136,6 +139,23 @@ class HeatEquation:
         defect = device_vector(self.g_vec, self.N_Y) - self.B @ u
         return residual.dot(self.P @ residual), defect.dot(self.K @ defect)
 
+    def sample(self, u, times, points):
+        """u_h(t_k, x_p) of a trial-space vector `u` -- the flat NumPy vector of the
+        serial operators or a device vector (source.linop.device_vector) -- at `times`
+        (n_k,) in [0, T] and `points` (n_p, d): an (n_k, n_p) device tensor, NaN at points
+        outside the mesh.  The plan of heateq_mpi.py's sample() (source/sampling.py,
+        csrc/sample.hip), built by the first call.  Test-space vectors (discontinuous in
+        time) and paired lists (t_p, x_p) are out of scope."""
+        from source.linop import _is_device_vector
+        from source.sampling import SamplePlan, sample_collective
+        if not _is_device_vector(u):
+            u = device_vector(u, self.N)
+        assert u.N == self.N and u.M == self.M, 'sample() takes vectors of the trial space'
+        if self.sample_plan is None:
+            mesh_space, mesh_time = self._sample_meshes
+            self.sample_plan = SamplePlan(mesh_space, mesh_time)
+        return sample_collective(self.sample_plan, u, times, points)
+
 
 _OPTIONS = (
     ('problem', str, 'square', 'problem type (square, lshape, cube, square_forced, cube_forced,'
@@ -144,14 +164,14 @@ _OPTIONS = (
     ('J_space', int, 6, 'number of space refines'),
     ('precond', str, 'multigrid', 'spatial preconditioner: multigrid or direct.'),
     ('alpha', float, 0.3, 'Alpha value used in the preconditioner for X.'),
-)
+) + driver.SAMPLE_OPTIONS  # taken off the command line again before the constructor sees it
 
 
 def main(argv=None):
     parser = argparse.ArgumentParser(description='Solve the heat equation, serial wiring.')
     for flag, kind, default, text in _OPTIONS:
         parser.add_argument('--' + flag, type=kind, default=default, help=text)
-    args = parser.parse_args(argv)
+    args, sampling = driver.take_sample_options(parser.parse_args(argv))
     print('Arguments: %s' % args)
     print('\n\nCreating HeatEquation with %d time refines and %d space refines.'
           % (args.J_time, args.J_space))
@@ -161,6 +181,8 @@ def main(argv=None):
     u, iters = heat.solve(callback=lambda w, residual, k: print('.', end='', flush=True))
     print('Done in %d  PCG steps. X-norm algebraic error: %s. Error in Yprime: %s\n'
           % ((iters,) + heat.errors(u)))
+    if sampling is not None:
+        driver.write_samples(heat, u, sampling)
     return heat, u, iters
 
 

@@ -243,6 +243,8 @@ class HeatEquationMPI:
 
         mesh_space, bc_space, mesh_time, data, fn = problem_helper(
             problem, J_space=J_space, J_time=J_time)
+        # what sample() builds its plan from, on first use
+        self._sample_meshes, self.sample_plan = (mesh_space, mesh_time), None
         mark('meshes')
         # the load vector and the prolongations need the mesh only: beside the
         # assembly, which runs on the host threads of libstk (no GIL held)
@@ -518,6 +520,25 @@ class HeatEquationMPI:
         defect = self.g - self.B @ u
         return residual.dot(self.P @ residual), defect.dot(self.K_Y(defect))
 
+    def sample(self, u, times, points):
+        """u_h(t_k, x_p) of a trial-space vector `u` (KronVectorMPI: a solution, an iterate)
+        at `times` (n_k,) in [0, T] and `points` (n_p, d) -- NumPy array, device tensor, or
+        what ``sample_plan.locate`` returned -- as an (n_k, n_p) device tensor, NaN at
+        points outside the mesh.  COLLECTIVE: every rank evaluates the terms of the time
+        nodes it owns (source/sampling.py, csrc/sample.hip) and the block is all-reduced
+        with the communicator of the vectors; every term has one non-zero contributor, so
+        the block does not depend on the number of ranks, bit for bit, and every rank
+        returns all of it.  The plan (mesh and point-location grid on the device) is built
+        by the first call; a run that never samples builds nothing.  Test-space vectors
+        (discontinuous in time) and paired lists (t_p, x_p) are out of scope: a paired
+        list is the diagonal of a block."""
+        from source.sampling import SamplePlan, sample_collective
+        assert u.dofs_distr.N == self.N and u.M == self.M, 'sample() takes vectors of the trial space'
+        if self.sample_plan is None:
+            mesh_space, mesh_time = self._sample_meshes
+            self.sample_plan = SamplePlan(mesh_space, mesh_time)
+        return sample_collective(self.sample_plan, u, times, points)
+
     def print_time_per_apply(self):
         for name in driver.OPERATORS:
             print('%-4s%.5f\t%.5f' % ((name + ':',) + tuple(getattr(self, name).time_per_apply())))
@@ -533,7 +554,8 @@ def main(argv=None):
                                 'reference\'s arithmetic (r.Pr history within 1e-10 of the CPU '
                                 'path); fast: both regrouped everywhere (4 %% less solve time, history '
                                 'within 4.6e-10); reference: every regrouping of the build off '
-                                '(2.3x slower than fast)')])
+                                '(2.3x slower than fast)')] + list(driver.SAMPLE_OPTIONS))
+    args, sampling = driver.take_sample_options(args)
     comm, rank, size = driver.start(args)
     heat = HeatEquationMPI(**driver.solver_arguments(args))
     # per-rank record, gathered and printed as one blob at the end
@@ -591,6 +613,8 @@ def main(argv=None):
         if rank == 0:
             print('Done in %d  PCG steps. X-norm algebraic error: %s. Error in Yprime: %s\n'
                   % (iters, error_alg, error_Yprime))
+    if sampling is not None:
+        driver.write_samples(heat, solution, sampling, rank)  # collective
     driver.publish(comm, record)
     return heat, solution, iters, history
 

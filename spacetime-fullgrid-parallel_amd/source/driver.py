@@ -25,6 +25,12 @@ _PROBLEM_OPTIONS = (
     ('alpha', float, 0.3, 'alpha'),
 )
 OPERATORS = ('W', 'S', 'WT', 'P')
+# the solve drivers' options for sampling the solution (never constructor arguments)
+SAMPLE_OPTIONS = (
+    ('sample_out', str, None, 'write the solution sampled on a raster at equally spaced times to this .npz'),
+    ('sample_times', int, 5, 'number of equally spaced sample times from 0 to T'),
+    ('sample_raster', int, 129, 'raster points per axis over the bounding box of the mesh'),
+)
 
 
 def device_mb():
@@ -108,6 +114,31 @@ def time_operator(comm, op, vec, iters):
     return counters(op, time_applies_iter=per_apply,
                     time_communication_iter=per_exchange,
                     time_total=MPI.Wtime() - began)
+
+
+def take_sample_options(args):
+    """(the parsed command line without the sampling options, those options or None when
+    --sample_out is not given): what the drivers print and record stays what it was."""
+    sampling = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in SAMPLE_OPTIONS})
+    return args, (sampling if sampling.sample_out else None)
+
+
+def write_samples(heat, solution, args, rank=0):
+    """--sample_out: the solution on a raster of sample_raster^d points over the bounding
+    box at sample_times equally spaced times from 0 to T, written by rank 0 as an .npz with
+    times (K,), points (R^d, d), inside (R^d,) and values (K, R^d).  Collective
+    (heat.sample); works for both solve drivers."""
+    from .sampling import raster
+    mesh_space, mesh_time = heat._sample_meshes
+    times = np.linspace(0.0, mesh_time.T, args.sample_times)
+    points = raster(mesh_space, args.sample_raster)
+    values = heat.sample(solution, times, points)
+    located = heat.sample_plan.locate(points)
+    if rank == 0:
+        with open(args.sample_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
+            np.savez(f, times=times, points=points, inside=located.inside.cpu().numpy(),
+                     values=values.cpu().numpy())
+    return values
 
 
 def publish(comm, record):

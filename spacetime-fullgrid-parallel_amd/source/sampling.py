@@ -1,0 +1,176 @@
+"""Sampling the discrete solution: u_h(t_k, x_p) at arbitrary points and times, on the
+device (csrc/sample.hip, include/stk.h "sampling the trial space").
+
+A solution is a slab of nodal values in free-dof order; this module is what reads it:
+rasters of time slices, probes at points, cuts along lines.
+
+* ``SamplePlan(mesh)``: the mesh, the vertex -> slab-row map and a bucket grid for point
+  location on the device, built once.  ``locate(points)`` finds the cell and the
+  barycentric coordinates of every point; ``evaluate(vec, times, located)`` returns this
+  rank's contribution to the ``(n_k, n_p)`` block of values.
+* ``time_weights``: which two time nodes a time lies between, with which weights, and
+  which of them a rank owns (pure NumPy).
+* ``raster``: a regular grid of points over the bounding box (pure NumPy).
+* ``bucket_grid``: the point-location grid as host arrays (no GPU needed).
+
+Scope: vectors of the TRIAL space (continuous piecewise linear in time) and the full
+points x times block.  Test-space vectors (discontinuous in time) and paired lists
+(t_p, x_p) are not served; a paired list is the diagonal of a block.
+"""
+import ctypes
+
+import numpy as np
+
+
+def _mesh_arrays(mesh):
+    pts = np.ascontiguousarray(mesh.points, dtype=np.float64)
+    cells = np.ascontiguousarray(mesh.cells, dtype=np.int64)
+    return pts, cells, cells.shape[1] - 1
+
+
+def bucket_grid(mesh):
+    """The point-location grid of a mesh, built on the host threads of libstk
+    (stk_sample_grid_build): dict with bins (d,), lo (d,) = the shifted corner,
+    inv_width (d,), widen, bin_ptr, bin_cells (CSR: the cells of bin
+    ``(iz bins[1] + iy) bins[0] + ix`` in ascending order)."""
+    from . import _lib
+    pts, cells, d = _mesh_arrays(mesh)
+    lib, grid = _lib.lib(), ctypes.c_void_p()
+    _lib.check(lib.stk_sample_grid_build(d, len(pts), len(cells), pts.ctypes.data, cells.ctypes.data,
+                                         ctypes.byref(grid)))
+    try:
+        bins, lo, inv_w = np.zeros(3, np.int32), np.zeros(3), np.zeros(3)
+        widen, entries = ctypes.c_double(), ctypes.c_int64()
+        _lib.check(lib.stk_sample_grid_sizes(grid, bins.ctypes.data, lo.ctypes.data, inv_w.ctypes.data,
+                                             ctypes.addressof(widen), ctypes.addressof(entries)))
+        bin_ptr = np.empty(int(np.prod(bins[:d], dtype=np.int64)) + 1, np.int32)
+        bin_cells = np.empty(entries.value, np.int32)
+        _lib.check(lib.stk_sample_grid_copy(grid, bin_ptr.ctypes.data, bin_cells.ctypes.data))
+    finally:
+        lib.stk_sample_grid_free(grid)
+    return {'bins': bins[:d].copy(), 'lo': lo[:d].copy(), 'inv_width': inv_w[:d].copy(), 'widen': widen.value,
+            'bin_ptr': bin_ptr, 'bin_cells': bin_cells}
+
+
+def time_weights(mesh_time, times, t_begin, t_end):
+    """(columns (n_k, 2) int32, weights (n_k, 2)) of the times on a rank that owns the
+    time nodes [t_begin, t_end): with h the element length and N the number of nodes,
+    e = min(floor(t / h), N - 2), s = t / h - e, weights (1 - s, s); column a is
+    e + a - t_begin where the rank owns node e + a, else -1.  Times outside [0, T]
+    raise ValueError."""
+    times = np.atleast_1d(np.asarray(times, dtype=np.float64))
+    if times.ndim != 1:
+        raise ValueError('times must be one-dimensional')
+    N, h, T = mesh_time.nv, mesh_time.h, mesh_time.T
+    if N < 2:
+        raise ValueError('a time mesh of one node has no element')
+    if not np.all((times >= 0.0) & (times <= T)):  # also refuses NaN
+        raise ValueError('times outside [0, %g]' % T)
+    x = times / h
+    e = np.minimum(np.floor(x), N - 2).astype(np.int64)
+    s = x - e
+    nodes = e[:, None] + np.arange(2)[None, :]
+    owned = (nodes >= t_begin) & (nodes < t_end)
+    columns = np.where(owned, nodes - t_begin, -1).astype(np.int32)
+    weights = np.stack([1.0 - s, s], axis=1)
+    return np.ascontiguousarray(columns), np.ascontiguousarray(weights)
+
+
+def raster(mesh, n):
+    """The n^d points of a regular grid over the bounding box of the mesh (both ends
+    included), shape (n^d, d); the first coordinate runs fastest."""
+    pts = np.asarray(mesh.points, dtype=np.float64)
+    d = pts.shape[1]
+    axes = [np.linspace(pts[:, k].min(), pts[:, k].max(), int(n)) for k in range(d)]
+    grids = np.meshgrid(*axes[::-1], indexing='ij')[::-1]
+    return np.stack([g.reshape(-1) for g in grids], axis=1)
+
+
+class Located:
+    """Points located in a mesh: device tensors ``cell`` (n_p,) int32 (-1 = outside),
+    ``lam`` (n_p, d + 1) and ``inside`` (n_p,) bool."""
+    def __init__(self, cell, lam):
+        self.cell, self.lam = cell, lam
+        self.inside = cell >= 0
+        self.n_p = cell.shape[0]
+
+
+class SamplePlan:
+    """The sampling engine of libstk on one mesh.  ``mesh_time``: the time mesh of the
+    vectors (default: the uniform mesh of [0, 1] with the vector's number of nodes, which
+    is what source/problem.py builds).  Not for two streams at once: the plan owns the
+    request tables of a call in flight."""
+    def __init__(self, mesh, mesh_time=None):
+        import torch
+
+        from . import _lib
+        from .assembly import free_dofs
+        self._lib = _lib
+        self.mesh_time = mesh_time
+        pts, cells, self.d = _mesh_arrays(mesh)
+        fd = np.ascontiguousarray(free_dofs(mesh), dtype=np.int64)
+        self.n_free = len(fd)
+        self._plan = ctypes.c_void_p()
+        # the library held by the closure: __del__ may run at interpreter exit
+        self._destroy = lambda plan, lib=_lib.lib(): lib.stk_sample_plan_destroy(plan)
+        with torch.cuda.device(_lib.compute_device()):
+            _lib.check(_lib.lib().stk_sample_plan_create(
+                self.d, len(pts), len(cells), pts.ctypes.data, cells.ctypes.data, self.n_free, fd.ctypes.data,
+                ctypes.byref(self._plan)))
+
+    def __del__(self):
+        if getattr(self, '_plan', None):
+            self._destroy(self._plan)
+            self._plan = None
+
+    def locate(self, points):
+        """points: (n_p, d) NumPy array or device tensor (or what locate returned)."""
+        import torch
+        _lib = self._lib
+        if isinstance(points, Located):
+            return points
+        if not torch.is_tensor(points):
+            points = torch.from_numpy(np.array(points, dtype=np.float64, order='C'))  # a copy: torch wants it writable
+        assert points.ndim == 2 and points.shape[1] == self.d, tuple(points.shape)
+        x = points.to(device=_lib.compute_device(), dtype=torch.float64).t().contiguous()  # [d][n_p]
+        n_p = x.shape[1]
+        cell = torch.empty(n_p, dtype=torch.int32, device=x.device)
+        lam = torch.empty((n_p, self.d + 1), dtype=torch.float64, device=x.device)
+        if n_p:
+            _lib.check(_lib.lib().stk_sample_locate(_lib.stream(), self._plan, n_p, _lib.ptr(x), _lib.ptr(cell),
+                                                    _lib.ptr(lam)))
+        return Located(cell, lam)
+
+    def evaluate(self, vec, times, located, out=None):
+        """This rank's contribution to u_h(t_k, x_p) of the trial-space vector `vec`
+        (KronVectorMPI), shape (n_k, n_p): the terms of the time nodes this rank owns,
+        exactly 0.0 for the others, NaN at points outside the mesh.  The sum over the
+        ranks is the value (HeatEquationMPI.sample all-reduces it)."""
+        import torch
+        _lib = self._lib
+        mesh_time = self.mesh_time
+        if mesh_time is None:
+            from .mesh import construct_interval
+            mesh_time = construct_interval(N=vec.N - 1)
+        assert mesh_time.nv == vec.N, (mesh_time.nv, vec.N)
+        assert vec.M == self.n_free, (vec.M, self.n_free)
+        columns, weights = time_weights(mesh_time, times, vec.t_begin, vec.t_end)
+        n_k, n_p = len(columns), located.n_p
+        if out is None:
+            out = torch.empty((n_k, n_p), dtype=torch.float64, device=vec.buf.device)
+        assert tuple(out.shape) == (n_k, n_p) and out.is_contiguous() and out.dtype == torch.float64
+        if n_k and n_p:
+            _lib.check(_lib.lib().stk_sample_eval(
+                _lib.stream(), self._plan, n_p, _lib.ptr(located.cell), _lib.ptr(located.lam), vec.M, vec.n_loc, vec.ld,
+                _lib.ptr(vec.buf), n_k, columns.ctypes.data, weights.ctypes.data, n_p, _lib.ptr(out)))
+        return out
+
+
+def sample_collective(plan, vec, times, points):
+    """The full (n_k, n_p) block on every rank: the local contributions all-reduced with
+    the communicator of the vector, the pattern of KronVectorMPI.dot -- every term has
+    exactly one non-zero contributor, so the block is the one-rank block bit for bit
+    whatever the rank count."""
+    block = plan.evaluate(vec, times, plan.locate(points))
+    vec.dofs_distr.comm.allreduce_tensor_(block)
+    return block
