@@ -659,10 +659,10 @@ int stk_ell_spmm(void *stream, const stk_ell_rows *ell_host, int32_t n_loc,
  * permutation, two triangular solves, column permutation -- runs on the device,
  * level-scheduled: wide levels of the elimination tree one launch each, runs of
  * narrow levels inside one workgroup (csrc/sptrsv.hip).  L and U: CSR on the host
- * (sorted columns; L unit lower triangular, U upper with its diagonal), perm_r /
- * perm_c: SuperLU.perm_r / perm_c (NULL = identity).  The sums of a row have one
- * shape whatever the slab length: the result does not depend on the partition of
- * the time axis.  work: M * ld device doubles; b may be x. */
+ * (sorted columns; L unit lower triangular, its diagonal stored or not, U upper with its
+ * diagonal), perm_r / perm_c: SuperLU.perm_r / perm_c (NULL = identity).  The sums
+ * of a row have one shape whatever the slab length: the result does not depend on the
+ * partition of the time axis.  work: M * ld device doubles; b may be x. */
 typedef struct stk_lu stk_lu;
 int stk_lu_create(int32_t n, const int32_t *L_indptr, const int32_t *L_indices,
                   const double *L_data, const int32_t *U_indptr,
@@ -687,8 +687,9 @@ int stk_lu_solve(stk_lu *lu, void *stream, int32_t n_loc, int32_t ld,
  *   per block k descending: z_k = inv(U_kk) (y_k - U[k, >k] z_>k), head levels
  * with one launch per block.  block = n_top: the explicit inverses of the whole blocks
  * (two launches per solve, five to ten times the rounding error of substitution); 256
- * keeps the accuracy of substitution.  Without the call the plan walks every level (a
- * run of narrow levels in one workgroup). */
+ * keeps the accuracy of substitution.  The inverted blocks are read WITH their diagonal:
+ * inv(L_kk) carries its ones whether or not L stores its unit diagonal.  Without the call
+ * the plan walks every level (a run of narrow levels in one workgroup). */
 int stk_lu_top_rows(const stk_lu *lu, int32_t *n_top, int32_t *rows_host);
 int stk_lu_set_top_inverse(stk_lu *lu, const double *L_blocks_dev,
                            const double *U_blocks_dev, int32_t block);

@@ -117,6 +117,30 @@ class SpaceMatrix(SpaceOp):
         return out
 
 
+def invert_top_blocks(L, U, rows, block):
+    """The two dense device blocks stk_lu_set_top_inverse takes: L[rows, rows] and
+    U[rows, rows] (CSR factors, `rows` from stk_lu_top_rows) as dense matrices whose DIAGONAL
+    BLOCKS of `block` rows are replaced by their inverses (LAPACK's triangular inverse on the
+    host, at set-up like the factorisation itself; hipBLAS' trsm fails to allocate on this
+    image).  L is unit lower triangular with its diagonal stored or not (include/stk.h): the
+    inverse of a unit block carries its ones explicitly, because the device multiplies by the
+    diagonal entry -- dtrtri(unitdiag=1) neither reads nor writes it."""
+    from scipy.linalg.lapack import dtrtri
+    n_top = len(rows)
+    blocks = []
+    for T, lower, unit in ((L, 1, 1), (U, 0, 0)):
+        dense = np.ascontiguousarray(T[rows][:, rows].toarray())
+        for a in range(0, n_top, block):
+            e = min(a + block, n_top)
+            inv, info = dtrtri(np.asfortranarray(dense[a:e, a:e]), lower=lower, unitdiag=unit)
+            assert info == 0, info
+            if unit:
+                np.fill_diagonal(inv, 1.0)
+            dense[a:e, a:e] = inv
+        blocks.append(_lib.to_dev(dense))
+    return blocks
+
+
 class InvLinOp(SpaceOp):
     """Direct inverse as a space operator (reference linop.py:18-26, used by
     precond='direct', heateq_mpi.py:154-157).  The factorisation is SuperLU on
@@ -181,22 +205,10 @@ class InvLinOp(SpaceOp):
             n_top = ctypes.c_int32()
             _lib.check(lib.stk_lu_top_rows(plan, ctypes.byref(n_top), None))
             if 0 < n_top.value <= self.DENSE_TOP_MAX and self.dense_top:
-                from scipy.linalg.lapack import dtrtri
                 rows = np.empty(n_top.value, dtype=np.int32)
                 _lib.check(lib.stk_lu_top_rows(plan, ctypes.byref(n_top), rows.ctypes.data))
-                blocks = []
                 nb = min(self.TOP_BLOCK, n_top.value)
-                for T, lower, unit in ((L, 1, 1), (U, 0, 0)):
-                    # the block as a dense matrix with its DIAGONAL BLOCKS of nb rows inverted
-                    # (LAPACK's triangular inverse on the host, at set-up like the
-                    # factorisation itself; hipBLAS' trsm fails to allocate on this image)
-                    dense = np.ascontiguousarray(T[rows][:, rows].toarray())
-                    for a in range(0, n_top.value, nb):
-                        e = min(a + nb, n_top.value)
-                        inv, info = dtrtri(np.asfortranarray(dense[a:e, a:e]), lower=lower, unitdiag=unit)
-                        assert info == 0, info
-                        dense[a:e, a:e] = inv
-                    blocks.append(_lib.to_dev(dense))
+                blocks = invert_top_blocks(L, U, rows, nb)
                 _lib.check(lib.stk_lu_set_top_inverse(plan, _lib.ptr(blocks[0]), _lib.ptr(blocks[1]), nb))
                 self.n_top = int(n_top.value)
             self._plan = plan
