@@ -1162,6 +1162,78 @@ int stk_sample_eval(void *stream, stk_sample_plan *plan, int64_t n_p,
                     int32_t ld, const double *slab, int32_t n_k, const int32_t *columns,
                     const double *weights, int64_t ld_out, double *out);
 
+/* ---- space-time error norms: || u - u_h || by quadrature on the device --------------
+ * The error of a trial-space vector (continuous P1 in time on a uniform mesh, P1 on a
+ * simplicial mesh in space) against a function the caller evaluates at quadrature points:
+ * its square in L2 and in the H1 seminorm of the mesh, integrated over ONE time element
+ * per call, without downloading the slab and without an interpolant standing in for u.
+ *
+ * The PLAN is built once per mesh from the HOST arrays stk_load_plan_create and
+ * stk_sample_plan_create take, with their checks: points [nv][d], cells [nc][d + 1]
+ * (d = 2 or 3), free_vertices [n_free] = the vertex of every slab row.  Nothing assumes
+ * that the cells cover anything.  It uploads the cells (int32) and the map vertex -> slab
+ * row (-1 for a boundary vertex, whose value is 0), and computes per cell |T| by the
+ * expressions of stk_load_plan_create and the gradients of the barycentric coordinates
+ * [nc][d + 1][d]: with e_r = p_r - p_0,
+ *     triangles   det = e1[0] e2[1] - e1[1] e2[0],
+ *                 grad l_1 = (e2[1] / det, -e2[0] / det),  grad l_2 = (-e1[1] / det, e1[0] / det);
+ *     tetrahedra  det = (e1[0] C_00 + e1[1] C_10) + e1[2] C_20 with the cofactors
+ *                 (C_0a, C_1a, C_2a) = e2 x e3, e3 x e1, e1 x e2 for a = 0, 1, 2, each
+ *                 component a difference of two products,
+ *                 grad l_(a+1)[j] = C_ja / det;
+ *     grad l_0[j] = -((grad l_1[j] + grad l_2[j]) [+ grad l_3[j]]),
+ * each quotient rounded once.  The plan owns 4 ceil(nc / 256) doubles of workspace for
+ * the tile partials of a call in flight: one plan serves one stream at a time.
+ *
+ * The rule is the caller's, per call, as for the load vectors: HOST arrays rule_points
+ * [nq][d + 1] (barycentric) and rule_weights [nq], 1 <= nq <= STK_ERR_MAX_NQ.
+ * stk_err_points writes the DEVICE array q_points [d][nc][nq] by the expression of
+ * stk_load_points -- the same doubles.
+ *
+ * stk_err_element takes, for the n_k (1..STK_ERR_MAX_K) time points of one time element,
+ * HOST arrays w_lo, w_hi, c [n_k] and DEVICE arrays f [n_k][nc][nq] (the exact solution at
+ * the quadrature points) and gf [n_k][d][nc][nq] (its gradient; NULL = no H1 part), and
+ * the nodal values at the two ends of the element: u_lo / u_hi point at row 0 of the
+ * lower / upper time node, consecutive rows stride_lo / stride_hi doubles apart (a slab
+ * column: ld; a contiguous row such as a ghost row: 1).  One lane per cell, a workgroup
+ * per tile of 256 consecutive cells.  Per cell with vertices a = 0 .. d, every product
+ * and every sum rounded on its own (no fused multiply-adds):
+ *     U_a  = w_lo[k] lo_a + w_hi[k] hi_a       (0.0 for a boundary vertex; no row is read)
+ *     uh_q = ((l_q0 U_0 + l_q1 U_1) + l_q2 U_2) [+ l_q3 U_3]
+ *     E_k  = sum_q ((f_q - uh_q)^2) w_q,    R_k = sum_q (f_q^2) w_q      q ascending from 0.0
+ *     G_j  = ((U_0 grad l_0[j] + U_1 grad l_1[j]) + U_2 grad l_2[j]) [+ U_3 grad l_3[j]]
+ *     EG_k = sum_j [sum_q ((gf_qj - G_j)^2) w_q],  RG_k the same with G_j = 0,
+ *            the inner sum first from 0.0, j ascending from 0.0
+ *     the cell's four numbers:  sum_k c[k] (X_k |T|),  k ascending, the first product
+ *            starting the sum,  X = E, EG, R, RG.
+ * The sum over the cells has one shape, fixed by nc: tile i is cells [256 i, 256 i + 256)
+ * whatever the grid; its 256 lanes (absent cells: 0.0) are added in the tree
+ * x[i] += x[i + s], s = 128, 64, .., 1; the tile partials are added by one workgroup in the
+ * same tree over the tile index, s = P / 2, .., 1 with P the power of two at or above the
+ * number of tiles (an absent partner adds nothing).  No atomics.  The result is the
+ * DEVICE array out4 = (err_L2^2, err_H1^2, ref_L2^2, ref_H1^2): the integrals of
+ * (u - u_h)^2, |grad (u - u_h)|^2, u^2, |grad u|^2 over the element when c[k] carries the
+ * time rule's weights; entries 1 and 3 are 0.0 without gf.  Offsets into f and gf are
+ * 64-bit; lanes beyond nc read nothing.  A null pointer (gf excepted), n_k or nq out of
+ * range or a stride below 1 is refused with out4 untouched.  The plan checks indices, not
+ * geometry (as the load plan): a degenerate cell (det = 0) has |T| = 0 and gradients that
+ * are inf or NaN, which reach the H1 sums unannounced. */
+#define STK_ERR_MAX_NQ 16
+#define STK_ERR_MAX_K 16
+typedef struct stk_err_plan stk_err_plan;
+int stk_err_plan_create(int32_t d, int64_t nv, int64_t nc, const double *points,
+                        const int64_t *cells, int64_t n_free,
+                        const int64_t *free_vertices, stk_err_plan **out);
+int stk_err_plan_destroy(stk_err_plan *plan);
+int stk_err_points(void *stream, const stk_err_plan *plan, int32_t nq,
+                   const double *rule_points, double *q_points);
+int stk_err_element(void *stream, stk_err_plan *plan, int32_t nq,
+                    const double *rule_weights, const double *rule_points, int32_t n_k,
+                    const double *w_lo, const double *w_hi, const double *c,
+                    const double *f, const double *gf, const double *u_lo,
+                    int64_t stride_lo, const double *u_hi, int64_t stride_hi,
+                    double *out4);
+
 /* ---- plan construction on the host threads: processing order and union pattern ---
  * stk_tile_order: the mesh-tile order of n dofs with coordinates coords [n][d]
  * (d = 2 or 3): the bounding box cut into cubes of edge `side` from the corner `lo`

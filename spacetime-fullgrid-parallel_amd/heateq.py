@@ -45,6 +45,8 @@ class HeatEquation:
                                                              J_time=J_time)
         # what sample() builds its plan from, on first use
         self._sample_meshes, self.sample_plan = (mesh_space, mesh_time), None
+        # ... and error_norms() its plan, with the problem's exact solution if it has one
+        self.error_plan, self._exact = None, (data.get('exact'), data.get('exact_grad'))
         A_t, L_t, M_t, G_t, u0_t = time_matrices(mesh_time)
         M_Y, Minv_Y, B1_t, B2_t = time_matrices_test_space(mesh_time)
         M_x, A_x = space_matrices(mesh_space)
@@ -156,6 +158,26 @@ class HeatEquation:
             self.sample_plan = SamplePlan(mesh_space, mesh_time)
         return sample_collective(self.sample_plan, u, times, points)
 
+    def error_norms(self, u, exact=None, exact_grad=None, times=None):
+        """|| u - u_h || of a trial-space vector `u` -- flat NumPy vector or device vector
+        -- against `exact` (default: the problem's data['exact'] and data['exact_grad']) in
+        L2(I; L2), L2(I; H^1_0) and in L2(Omega) at `times` (default [T]): the dict of
+        heateq_mpi.py's error_norms() (source/error_norms.py, csrc/err_norms.hip); the plan
+        is built by the first call."""
+        from source.error_norms import ErrorPlan, error_norms_collective
+        from source.linop import _is_device_vector
+        if not _is_device_vector(u):
+            u = device_vector(u, self.N)
+        assert u.N == self.N and u.M == self.M, 'error_norms() takes vectors of the trial space'
+        if exact is None:
+            exact, default_grad = self._exact
+            exact_grad = default_grad if exact_grad is None else exact_grad
+        assert exact is not None, 'this problem has no exact solution: pass exact='
+        if self.error_plan is None:
+            mesh_space, mesh_time = self._sample_meshes
+            self.error_plan = ErrorPlan(mesh_space, mesh_time)
+        return error_norms_collective(self.error_plan, u, exact, exact_grad, times)
+
 
 _OPTIONS = (
     ('problem', str, 'square', 'problem type (square, lshape, cube, square_forced, cube_forced,'
@@ -181,8 +203,10 @@ def main(argv=None):
     u, iters = heat.solve(callback=lambda w, residual, k: print('.', end='', flush=True))
     print('Done in %d  PCG steps. X-norm algebraic error: %s. Error in Yprime: %s\n'
           % ((iters,) + heat.errors(u)))
-    if sampling is not None:
+    if sampling is not None and sampling.sample_out:
         driver.write_samples(heat, u, sampling)
+    if sampling is not None and sampling.error_norms:
+        driver.report_error_norms(heat, u)  # this driver keeps no record: the line is the report
     return heat, u, iters
 
 

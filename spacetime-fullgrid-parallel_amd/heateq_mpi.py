@@ -245,6 +245,8 @@ class HeatEquationMPI:
             problem, J_space=J_space, J_time=J_time)
         # what sample() builds its plan from, on first use
         self._sample_meshes, self.sample_plan = (mesh_space, mesh_time), None
+        # ... and error_norms() its plan, with the problem's exact solution if it has one
+        self.error_plan, self._exact = None, (data.get('exact'), data.get('exact_grad'))
         mark('meshes')
         # the load vector and the prolongations need the mesh only: beside the
         # assembly, which runs on the host threads of libstk (no GIL held)
@@ -504,11 +506,14 @@ class HeatEquationMPI:
         out = self.Kinv_x.apply(y.buf, n_loc=y.n_loc)
         return KronVectorMPI.around(self.dofs_test, element_block_mix(self.dofs_test, self._minv_blocks, out))
 
-    def solve(self, callback=None, history=None):
+    def solve(self, callback=None, history=None, eps=1e-6, kmax=100000):
         """PCG on the wavelet-transformed system with the forcing's right-hand side
-        (reference heateq.py:146-150); returns (u = W w, iterations)."""
+        (reference heateq.py:146-150); returns (u = W w, iterations).  `eps`, `kmax`: PCG's
+        stopping rule (r.Pr < eps^2; the reference's 1e-6 by default) -- an algebraic error of
+        1e-6 in the energy norm shows in the fifth digit of || u - u_h || (error_norms), a
+        smaller eps removes it."""
         assert self.f is not None, 'solve() is the path of a problem with forcing; without: PCG on rhs'
-        w, iters = PCG(self.WT_S_W, self.P, self.WT @ self.f, callback=callback, history=history)
+        w, iters = PCG(self.WT_S_W, self.P, self.WT @ self.f, eps=eps, kmax=kmax, callback=callback, history=history)
         return self.W @ w, iters
 
     def errors(self, u):
@@ -538,6 +543,30 @@ class HeatEquationMPI:
             mesh_space, mesh_time = self._sample_meshes
             self.sample_plan = SamplePlan(mesh_space, mesh_time)
         return sample_collective(self.sample_plan, u, times, points)
+
+    def error_norms(self, u, exact=None, exact_grad=None, times=None):
+        """|| u - u_h || of a trial-space vector `u` (KronVectorMPI) against `exact`
+        (t, x, y[, z]) -- a pointwise function of float64 tensors that broadcast, evaluated on
+        the device; default: the problem's data['exact'] -- in L2(I; L2), in L2(I; H^1_0) if
+        `exact_grad` (default data['exact_grad'] when `exact` is the default too) is given, and
+        in L2(Omega) at `times` (default [T]), by quadrature on the device
+        (source/error_norms.py, csrc/err_norms.hip).  Returns a dict: l2_l2, l2_h1,
+        exact_l2_l2, exact_l2_h1 (the norms of u by the same rule, for relative errors), l2_at
+        (array over times) and per_element ((N - 1, 4) squares); H1 entries None without a
+        gradient.  COLLECTIVE: every rank integrates the time elements whose upper node it
+        owns and the per-element numbers are all-reduced with one contributor each, so every
+        entry is the one-rank double whatever the number of ranks.  The plan is built by the
+        first call; a run that never asks builds nothing."""
+        from source.error_norms import ErrorPlan, error_norms_collective
+        assert u.dofs_distr.N == self.N and u.M == self.M, 'error_norms() takes vectors of the trial space'
+        if exact is None:
+            exact, default_grad = self._exact
+            exact_grad = default_grad if exact_grad is None else exact_grad
+        assert exact is not None, 'this problem has no exact solution: pass exact='
+        if self.error_plan is None:
+            mesh_space, mesh_time = self._sample_meshes
+            self.error_plan = ErrorPlan(mesh_space, mesh_time)
+        return error_norms_collective(self.error_plan, u, exact, exact_grad, times)
 
     def print_time_per_apply(self):
         for name in driver.OPERATORS:
@@ -613,8 +642,12 @@ def main(argv=None):
         if rank == 0:
             print('Done in %d  PCG steps. X-norm algebraic error: %s. Error in Yprime: %s\n'
                   % (iters, error_alg, error_Yprime))
-    if sampling is not None:
+    if sampling is not None and sampling.sample_out:
         driver.write_samples(heat, solution, sampling, rank)  # collective
+    if sampling is not None and sampling.error_norms:
+        norms = driver.report_error_norms(heat, solution, rank)  # collective
+        if norms is not None:
+            record.update(error_norms=norms)
     driver.publish(comm, record)
     return heat, solution, iters, history
 

@@ -30,6 +30,8 @@ SAMPLE_OPTIONS = (
     ('sample_out', str, None, 'write the solution sampled on a raster at equally spaced times to this .npz'),
     ('sample_times', int, 5, 'number of equally spaced sample times from 0 to T'),
     ('sample_raster', int, 129, 'raster points per axis over the bounding box of the mesh'),
+    ('error_norms', int, 0, '1: after the solve, the L2(L2), L2(H1) and final-time L2 norms of the error against'
+     ' the exact solution of the problem, by quadrature on the device'),
 )
 
 
@@ -118,9 +120,30 @@ def time_operator(comm, op, vec, iters):
 
 def take_sample_options(args):
     """(the parsed command line without the sampling options, those options or None when
-    --sample_out is not given): what the drivers print and record stays what it was."""
+    neither --sample_out nor --error_norms is given): what the drivers print and record
+    stays what it was."""
     sampling = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in SAMPLE_OPTIONS})
-    return args, (sampling if sampling.sample_out else None)
+    return args, (sampling if sampling.sample_out or sampling.error_norms else None)
+
+
+def report_error_norms(heat, solution, rank=0):
+    """--error_norms: one line with the four norms of u - u_h and the relative errors
+    (heat.error_norms, collective; works for both solve drivers), and the dict for the
+    record (arrays as lists).  A problem without data['exact'] says so and returns None."""
+    if heat._exact[0] is None:
+        if rank == 0:
+            print('Error norms: this problem has no exact solution; nothing to compare with.')
+        return None
+    n = heat.error_norms(solution)
+    if rank == 0:
+        line = 'Error norms: L2(L2) %.6e (relative %.4e)' % (n['l2_l2'], n['l2_l2'] / n['exact_l2_l2'])
+        if n['l2_h1'] is not None:
+            line += ', L2(H1) %.6e (relative %.4e)' % (n['l2_h1'], n['l2_h1'] / n['exact_l2_h1'])
+        line += ', L2 at T %.6e; exact: L2(L2) %.6e' % (n['l2_at'][-1], n['exact_l2_l2'])
+        if n['l2_h1'] is not None:
+            line += ', L2(H1) %.6e' % n['exact_l2_h1']
+        print(line)
+    return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in n.items()}
 
 
 def write_samples(heat, solution, args, rank=0):

@@ -13,7 +13,13 @@ s_kl = sin(k pi x) sin(l pi y),
     square:  u = exp(-t) s_11 + t s_21,   g = (2 pi^2 - 1) exp(-t) s_11 + (1 + 5 pi^2 t) s_21,
     cube:    u = exp(-t) s_111 + t s_211, g = (3 pi^2 - 1) exp(-t) s_111 + (1 + 6 pi^2 t) s_211,
 u(0) = s_11 (s_111): two pairs whose space factors differ.  ``data['exact']`` is u
-as a function (t, x, y[, z]) of arrays, for the tests.
+as a function (t, x, y[, z]) of arrays -- NumPy arrays or torch tensors that broadcast --
+and ``data['exact_grad']`` its spatial gradient, a tuple of d arrays: what
+``error_norms`` (source/error_norms.py) integrates against.  All four manufactured
+problems (these two and the two ``*_nonseparable`` ones) carry both.  ``exact`` of the
+forced problems evaluates HOST tensors with NumPy (detached; the doubles of the NumPy
+call) and device tensors with torch on the device, whose sin and exp may differ from
+NumPy's in the last place.
 
 An entry of ``data['g']`` may also be a CALLABLE g(t, x, y[, z]): a pointwise function of
 float64 arrays that broadcast, for right-hand sides that are no short separable sum.
@@ -97,26 +103,6 @@ def _s211(x, y, z):
     return np.sin(2 * np.pi * x) * np.sin(np.pi * y) * np.sin(np.pi * z)
 
 
-def _forced_data(d, first, second):
-    """u = exp(-t) first + t second on [0,1]^d, where -laplace first = d pi^2 first
-    and -laplace second = (d + 3) pi^2 second: g = u_t - laplace u."""
-    pi2 = np.pi**2
-    g = [(lambda t: (d * pi2 - 1.0) * np.exp(-t), first),
-         (lambda t: 1.0 + (d + 3.0) * pi2 * t, second)]
-    exact = lambda t, *x: np.exp(-t) * first(*x) + t * second(*x)
-    return {'g': g, 'u0': first, 'exact': exact}
-
-
-def square_forced(J_space, J_time=None):
-    mesh_space, bc = construct_2d_square_mesh(nrefines=J_space)
-    return mesh_space, bc, _time_mesh(J_space, J_time), _forced_data(2, _u0, _s21), "square_forced"
-
-
-def cube_forced(J_space, J_time=None):
-    mesh_space, bc = construct_3d_cube_mesh(nrefines=J_space)
-    return mesh_space, bc, _time_mesh(J_space, J_time), _forced_data(3, _u0_3d, _s211), "cube_forced"
-
-
 def _array_module(*args):
     """torch if any argument is a torch tensor (subclasses included), else NumPy; torch
     is not imported for NumPy callers -- a tensor cannot exist before its module."""
@@ -128,6 +114,59 @@ def _array_module(*args):
 
 def _as_array(xp, v):
     return np.asarray(v, dtype=np.float64) if xp is np else xp.as_tensor(v, dtype=xp.float64)
+
+
+def _sine_product(xp, ks, x, cos_at=None):
+    """prod_c sin(k_c pi x_c) from the left, in the doubles of _u0 / _s21; with cos_at = j
+    the factor of axis j is replaced by its derivative k_j pi cos(k_j pi x_j)."""
+    out = None
+    for axis, (k, c) in enumerate(zip(ks, x)):
+        arg = np.pi * c if k == 1 else k * np.pi * c
+        factor = k * np.pi * xp.cos(arg) if axis == cos_at else xp.sin(arg)
+        out = factor if out is None else out * factor
+    return out
+
+
+def _forced_data(d, first, second):
+    """u = exp(-t) first + t second on [0,1]^d, where -laplace first = d pi^2 first
+    and -laplace second = (d + 3) pi^2 second: g = u_t - laplace u.  ``exact`` and
+    ``exact_grad`` take NumPy arrays or torch tensors (_array_module); on NumPy arrays
+    ``exact`` is the expression exp(-t) first(x) + t second(x) it always was, and host
+    tensors get those doubles; device tensors are evaluated by torch on the device."""
+    pi2 = np.pi**2
+    g = [(lambda t: (d * pi2 - 1.0) * np.exp(-t), first),
+         (lambda t: 1.0 + (d + 3.0) * pi2 * t, second)]
+    k_first, k_second = (1,) * d, (2,) + (1,) * (d - 1)
+
+    def exact(t, *x):
+        xp = _array_module(t, *x)
+        if xp is np:
+            return np.exp(-t) * first(*x) + t * second(*x)
+        t, x = _as_array(xp, t), [_as_array(xp, c) for c in x]
+        if not t.is_cuda and not any(c.is_cuda for c in x):
+            # host tensors: NumPy's sin and exp, so that the host has ONE set of doubles
+            # whichever array type carries them (torch's CPU kernels round some arguments
+            # one unit in the last place differently)
+            return xp.from_numpy(np.asarray(exact(t.detach().numpy(), *[c.detach().numpy() for c in x])))
+        return xp.exp(-t) * _sine_product(xp, k_first, x) + t * _sine_product(xp, k_second, x)
+
+    def exact_grad(t, *x):
+        xp = _array_module(t, *x)
+        t, x = _as_array(xp, t), [_as_array(xp, c) for c in x]
+        return tuple(xp.exp(-t) * _sine_product(xp, k_first, x, j) + t * _sine_product(xp, k_second, x, j)
+                     for j in range(d))
+
+    return {'g': g, 'u0': first, 'exact': exact, 'exact_grad': exact_grad}
+
+
+def square_forced(J_space, J_time=None):
+    mesh_space, bc = construct_2d_square_mesh(nrefines=J_space)
+    return mesh_space, bc, _time_mesh(J_space, J_time), _forced_data(2, _u0, _s21), "square_forced"
+
+
+def cube_forced(J_space, J_time=None):
+    mesh_space, bc = construct_3d_cube_mesh(nrefines=J_space)
+    return mesh_space, bc, _time_mesh(J_space, J_time), _forced_data(3, _u0_3d, _s211), "cube_forced"
 
 
 def _nonseparable_data(d):
@@ -149,7 +188,15 @@ def _nonseparable_data(d):
         xp, t, x0, s, rest, E = parts(t, x)
         return E * ((d * np.pi**2 - (1.0 + x0) - t * t) * s + 2.0 * t * np.pi * xp.cos(np.pi * x0) * rest)
 
-    return {'g': [g], 'u0': _u0 if d == 2 else _u0_3d, 'exact': exact}
+    def exact_grad(t, *x):
+        """grad u = E grad s + s grad E with grad E = (-t E, 0[, 0])."""
+        xp, t, x0, s, rest, E = parts(t, x)
+        x = [_as_array(xp, c) for c in x]
+        ks = (1,) * d
+        return tuple(E * (_sine_product(xp, ks, x, j) - t * s) if j == 0 else E * _sine_product(xp, ks, x, j)
+                     for j in range(d))
+
+    return {'g': [g], 'u0': _u0 if d == 2 else _u0_3d, 'exact': exact, 'exact_grad': exact_grad}
 
 
 def square_nonseparable(J_space, J_time=None):
