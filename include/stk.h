@@ -1141,7 +1141,47 @@ int stk_load_columns(void *stream, const stk_load_plan *plan, int32_t nq,
  * for the other: their sum over the ranks is the one-rank double.  Requests are served in
  * launches of at most 96 distinct columns each (one launch for a slab of up to 96 time
  * steps, whatever n_k).  The plan owns the request tables of a call in flight: one plan
- * serves one stream at a time.  No atomics. */
+ * serves one stream at a time.  No atomics.
+ *
+ * PAIRED REQUESTS AND DERIVATIVES.  stk_sample_pairs serves a list (t_p, x_p) -- a
+ * trajectory, a set of tracers -- without the (n_k, n_p) block it is the diagonal of, and
+ * returns, per point, any of u_h, its time derivative and its gradient.  It takes what
+ * stk_sample_locate wrote (cell [n_p], lam [n_p][d + 1]), t [n_p] DEVICE doubles, the
+ * element length h and number N >= 2 of nodes of the time mesh, the first node t_begin of
+ * this slab (n_loc valid columns, leading dimension ld, M = n_free rows), and `fields`,
+ * a mask: 1 = u, 2 = dt, 4 = grad.  out [n_rows][ld_out >= n_p] (64-bit addressing) holds
+ * the requested rows only, in the fixed order u, dt, grad_0 .. grad_(d-1).  Per point:
+ *     e = min(floor(t / h), N - 2),  s = t / h - e,  (w_0, w_1) = (1 - s, s)
+ * (the right-hand derivative at an interior node, the left-hand one at T); the nodes
+ * e, e + 1 are the local columns c_a = e + a - t_begin, and one outside [0, n_loc) is
+ * "not on this rank";
+ *     S(k, c) = ((k_0 u[v_0][c] + k_1 u[v_1][c]) + k_2 u[v_2][c]) [+ k_3 u[v_3][c]],
+ *     u      = w_0 S(lam, c_0) + w_1 S(lam, c_1),
+ *     dt     = (-(S(lam, c_0) / h)) + S(lam, c_1) / h,
+ *     grad_j = w_0 S(G_j, c_0) + w_1 S(G_j, c_1),   G_j[a] = d_j l_a of the located cell,
+ * every product, quotient and sum rounded on its own, a boundary vertex contributing the
+ * value 0.  A term whose column is absent is exactly 0.0 and its entries are not read; the
+ * padding column of an odd n_loc is never read.  Every requested field is NaN where
+ * cell < 0, where t is NaN and where t is outside [0, (N - 1) h]: the times are checked on
+ * the device, the call does not synchronise.  With the two columns of a point on different
+ * ranks each rank's out holds one term and 0.0 for the other; the sum over the ranks is
+ * the one-rank double.  One lane per point, no LDS, no atomics; n_p = 0 launches nothing;
+ * the plan is only read, so the call may share it with a stk_sample_eval in flight.
+ *
+ * The gradients of the barycentric coordinates are EVALUATED IN THE KERNEL, per point,
+ * from the vertices of the located cell by the expressions stk_sample_locate uses (the
+ * plan holds no table of them; its construction is unchanged): with e_r = p_r - p_0,
+ *     triangles   det = e1[0] e2[1] - e1[1] e2[0],
+ *                 grad l_1 = (e2[1] / det, (-e2[0]) / det),
+ *                 grad l_2 = ((-e1[1]) / det, e1[0] / det);
+ *     tetrahedra  det = e1 . (e2 x e3), summed from the left,
+ *                 grad l_1 = (e2 x e3) / det, grad l_2 = (e3 x e1) / det,
+ *                 grad l_3 = (e1 x e2) / det, every component a difference of two products;
+ *     grad l_0 = ((0 - grad l_1) - grad l_2) [- grad l_3],
+ * each quotient rounded once.  stk_sample_grad_coeffs writes the same doubles per located
+ * point, out [d][n_p][d + 1] (DEVICE; out[j][p][a] = d_j l_a, NaN for cell < 0): row j,
+ * passed to stk_sample_eval as `lam`, gives the (n_k, n_p) block of grad_j, and
+ * stk_sample_eval with the weights (-1 / h, 1 / h) gives the block of dt. */
 typedef struct stk_sample_grid stk_sample_grid;
 typedef struct stk_sample_plan stk_sample_plan;
 int stk_sample_grid_build(int32_t d, int64_t nv, int64_t nc, const double *points,
@@ -1161,6 +1201,12 @@ int stk_sample_eval(void *stream, stk_sample_plan *plan, int64_t n_p,
                     const int32_t *cell, const double *lam, int32_t M, int32_t n_loc,
                     int32_t ld, const double *slab, int32_t n_k, const int32_t *columns,
                     const double *weights, int64_t ld_out, double *out);
+int stk_sample_pairs(void *stream, const stk_sample_plan *plan, int64_t n_p,
+                     const int32_t *cell, const double *lam, const double *t, double h,
+                     int32_t N, int32_t t_begin, int32_t M, int32_t n_loc, int32_t ld,
+                     const double *slab, int32_t fields, int64_t ld_out, double *out);
+int stk_sample_grad_coeffs(void *stream, const stk_sample_plan *plan, int64_t n_p,
+                           const int32_t *cell, double *out);
 
 /* ---- space-time error norms: || u - u_h || by quadrature on the device --------------
  * The error of a trial-space vector (continuous P1 in time on a uniform mesh, P1 on a

@@ -11,6 +11,10 @@
 //                           cell with the largest smallest coordinate
 //  * stk_sample_eval        out[k][p] = w0 s_p(c0) + w1 s_p(c1) with the spatial sums
 //                           s_p(c) = ((l0 u[v0][c] + l1 u[v1][c]) + l2 u[v2][c]) [+ ...]
+//  * stk_sample_pairs       paired requests (t_p, x_p): one lane per point, u_h, its time
+//                           derivative and its gradient from 2 (d + 1) slab entries
+//  * stk_sample_grad_coeffs the gradients of the barycentric coordinates per located point:
+//                           as `lam` of stk_sample_eval they give the blocks of the gradient
 //
 // THE EVAL KERNEL.  A slab row is contiguous in time and a point needs d + 1 whole rows, so
 // the pass is a row gather, and its output is time-major: points x times turned through
@@ -268,6 +272,174 @@ __global__ __launch_bounds__(BS) void sample_eval_kernel(int64_t n_p, int64_t nc
             out[(int64_t)k * ld_out + p0 + p] = v;
         }
         __syncthreads();
+    }
+}
+
+// ---- gradients of the barycentric coordinates ---------------------------------------------
+// G[a][j] = d_j l_a of a cell, from the edge vectors, determinant and cross products that
+// barycentric() above forms: every quotient rounded once,
+// G[0] = ((0 - G[1]) - G[2]) [- G[3]].  Evaluated per point in the kernels below; the plan
+// holds no table, so its construction is what it was.
+template <int D>
+__device__ inline void barycentric_gradients(const double *__restrict__ pts, const int32_t *v, double (*G)[D])
+{
+    const double *p0 = pts + D * (int64_t)v[0];
+    double e[D][D];
+#pragma unroll
+    for (int r = 0; r < D; ++r)
+#pragma unroll
+        for (int k = 0; k < D; ++k) e[r][k] = pts[D * (int64_t)v[r + 1] + k] - p0[k];
+    if constexpr (D == 2) {
+        const double det = e[0][0] * e[1][1] - e[0][1] * e[1][0];
+        G[1][0] = e[1][1] / det, G[1][1] = (-e[1][0]) / det;
+        G[2][0] = (-e[0][1]) / det, G[2][1] = e[0][0] / det;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) G[0][j] = (0.0 - G[1][j]) - G[2][j];
+    } else {
+        double n[3][3];  // n[0] = e1 x e2, n[1] = e2 x e0, n[2] = e0 x e1
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double *a = e[(r + 1) % 3], *b = e[(r + 2) % 3];
+            n[r][0] = a[1] * b[2] - a[2] * b[1];
+            n[r][1] = a[2] * b[0] - a[0] * b[2];
+            n[r][2] = a[0] * b[1] - a[1] * b[0];
+        }
+        const double det = (e[0][0] * n[0][0] + e[0][1] * n[0][1]) + e[0][2] * n[0][2];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) G[r + 1][j] = n[r][j] / det;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) G[0][j] = ((0.0 - G[1][j]) - G[2][j]) - G[3][j];
+    }
+}
+
+// one lane per point: out [D][n_p][D + 1], the coefficients stk_sample_eval takes as `lam`
+template <int D>
+__global__ __launch_bounds__(BS) void sample_grad_coeffs_kernel(int64_t n_p, int64_t nc, const int32_t *__restrict__ cell,
+                                                                const double *__restrict__ pts,
+                                                                const int32_t *__restrict__ cells,
+                                                                double *__restrict__ out)
+{
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    for (int64_t p = (int64_t)blockIdx.x * BS + threadIdx.x; p < n_p; p += stride) {
+        const int32_t t = cell[p];
+        double G[D + 1][D];
+        if (t >= 0 && t < nc) {
+            int32_t v[D + 1];
+#pragma unroll
+            for (int a = 0; a <= D; ++a) v[a] = cells[(D + 1) * (int64_t)t + a];
+            barycentric_gradients<D>(pts, v, G);
+        } else {
+#pragma unroll
+            for (int a = 0; a <= D; ++a)
+#pragma unroll
+                for (int j = 0; j < D; ++j) G[a][j] = __builtin_nan("");
+        }
+#pragma unroll
+        for (int j = 0; j < D; ++j)
+#pragma unroll
+            for (int a = 0; a <= D; ++a) out[((int64_t)j * n_p + p) * (D + 1) + a] = G[a][j];
+    }
+}
+
+template <int D>
+__device__ inline double spatial_sum(const double *k, const double *v)
+{
+    double sum = k[0] * v[0];
+#pragma unroll
+    for (int a = 1; a <= D; ++a) sum = sum + k[a] * v[a];
+    return sum;
+}
+
+// THE PAIRS KERNEL: one lane per (t_p, x_p).  A point reads 2 (D + 1) slab entries -- the
+// two time columns of its D + 1 rows -- and nothing is shared between points, so there are
+// no tiles and no LDS.  All addresses are formed first and all loads issued before the
+// first sum: an absent column's address is replaced by the present one's and a boundary
+// vertex's row by row 0 (both values are then dropped), so no load sits behind a branch of
+// its own.  WIDE (even ld, 16-byte aligned slab): where both columns are present and the
+// first is even, the two adjacent doubles of a row come in one 16-byte load.  Every field
+// row of out is stored coalesced.
+template <int D, bool WIDE>
+__global__ __launch_bounds__(BS) void sample_pairs_kernel(int64_t n_p, int64_t nc, const int32_t *__restrict__ cell,
+                                                          const double *__restrict__ lam, const double *__restrict__ t,
+                                                          double h, double t_last, int32_t N, int32_t t_begin,
+                                                          int32_t n_loc, int32_t ld, const double *__restrict__ u,
+                                                          const double *__restrict__ pts,
+                                                          const int32_t *__restrict__ cells,
+                                                          const int32_t *__restrict__ row_of, int32_t fields,
+                                                          int64_t ld_out, double *__restrict__ out)
+{
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    const bool want_u = fields & 1, want_dt = fields & 2, want_grad = fields & 4;
+    for (int64_t p = (int64_t)blockIdx.x * BS + threadIdx.x; p < n_p; p += stride) {
+        const int32_t tc = cell[p];
+        const double tp = t[p];
+        const double nan = __builtin_nan("");
+        double val_u = nan, val_dt = nan, val_g[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) val_g[j] = nan;
+        if (tc >= 0 && tc < nc && tp >= 0.0 && tp <= t_last) {  // a NaN time fails both comparisons
+            const double x = tp / h;
+            double ef = floor(x);
+            if (ef > (double)(N - 2)) ef = (double)(N - 2);
+            const double w1 = x - ef, w0 = 1.0 - w1;
+            const int64_t c0 = (int64_t)ef - t_begin, c1 = c0 + 1;
+            const bool have0 = c0 >= 0 && c0 < n_loc, have1 = c1 >= 0 && c1 < n_loc;
+            int32_t v[D + 1], r[D + 1];
+#pragma unroll
+            for (int a = 0; a <= D; ++a) v[a] = cells[(D + 1) * (int64_t)tc + a];
+#pragma unroll
+            for (int a = 0; a <= D; ++a) r[a] = row_of[v[a]];
+            double l[D + 1], G[D + 1][D], u0[D + 1], u1[D + 1];
+#pragma unroll
+            for (int a = 0; a <= D; ++a) l[a] = lam[(D + 1) * p + a], u0[a] = u1[a] = 0.0;
+            if (have0 || have1) {
+                const double *row[D + 1];
+#pragma unroll
+                for (int a = 0; a <= D; ++a) row[a] = u + (int64_t)(r[a] < 0 ? 0 : r[a]) * ld;
+                if (WIDE && have0 && have1 && !(c0 & 1)) {
+#pragma unroll
+                    for (int a = 0; a <= D; ++a) {
+                        const double2 w = *reinterpret_cast<const double2 *>(row[a] + c0);
+                        u0[a] = w.x, u1[a] = w.y;
+                    }
+                } else {
+                    const int64_t ca = have0 ? c0 : c1, cb = have1 ? c1 : c0;
+#pragma unroll
+                    for (int a = 0; a <= D; ++a) u0[a] = row[a][ca], u1[a] = row[a][cb];
+                }
+#pragma unroll
+                for (int a = 0; a <= D; ++a)
+                    if (r[a] < 0) u0[a] = u1[a] = 0.0;
+            }
+            if (want_grad) barycentric_gradients<D>(pts, v, G);
+            if (want_u || want_dt) {
+                const double s0 = spatial_sum<D>(l, u0), s1 = spatial_sum<D>(l, u1);
+                const double a0 = have0 ? w0 * s0 : 0.0, a1 = have1 ? w1 * s1 : 0.0;
+                val_u = a0 + a1;
+                const double d0 = have0 ? -(s0 / h) : 0.0, d1 = have1 ? s1 / h : 0.0;
+                val_dt = d0 + d1;
+            }
+            if (want_grad) {
+#pragma unroll
+                for (int j = 0; j < D; ++j) {
+                    double k[D + 1];
+#pragma unroll
+                    for (int a = 0; a <= D; ++a) k[a] = G[a][j];
+                    const double a0 = have0 ? w0 * spatial_sum<D>(k, u0) : 0.0;
+                    const double a1 = have1 ? w1 * spatial_sum<D>(k, u1) : 0.0;
+                    val_g[j] = a0 + a1;
+                }
+            }
+        }
+        int64_t at = p;
+        if (want_u) out[at] = val_u, at += ld_out;
+        if (want_dt) out[at] = val_dt, at += ld_out;
+        if (want_grad) {
+#pragma unroll
+            for (int j = 0; j < D; ++j) out[at + j * ld_out] = val_g[j];
+        }
     }
 }
 
@@ -583,5 +755,56 @@ extern "C" int stk_sample_eval(void *stream, stk_sample_plan *plan, int64_t n_p,
                                slab, L.n_c, cols, L.n_kc, req, w, ld_out, o);
         STK_LAUNCH_CHECK();
     }
+    return 0;
+}
+
+extern "C" int stk_sample_grad_coeffs(void *stream, const stk_sample_plan *plan, int64_t n_p, const int32_t *cell,
+                                      double *out)
+{
+    const stk_timed timed_(STK_OP_SPACE, stream);
+    STK_REQUIRE(plan && n_p >= 0 && (n_p == 0 || (cell && out)), "stk_sample_grad_coeffs: bad arguments");
+    if (n_p == 0) return 0;
+    const dim3 grid(stk_flat_grid(n_p, BS));
+    hipStream_t st = stk_stream(stream);
+    if (plan->d == 2)
+        hipLaunchKernelGGL(sample_grad_coeffs_kernel<2>, grid, dim3(BS), 0, st, n_p, plan->nc, cell, plan->points, plan->cells,
+                           out);
+    else
+        hipLaunchKernelGGL(sample_grad_coeffs_kernel<3>, grid, dim3(BS), 0, st, n_p, plan->nc, cell, plan->points, plan->cells,
+                           out);
+    STK_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int stk_sample_pairs(void *stream, const stk_sample_plan *plan, int64_t n_p, const int32_t *cell,
+                                const double *lam, const double *t, double h, int32_t N, int32_t t_begin, int32_t M,
+                                int32_t n_loc, int32_t ld, const double *slab, int32_t fields, int64_t ld_out, double *out)
+{
+    const stk_timed timed_(STK_OP_SPACE, stream);
+    STK_REQUIRE(plan && n_p >= 0, "stk_sample_pairs: bad arguments");
+    STK_REQUIRE(fields >= 1 && fields <= 7, "stk_sample_pairs: fields=%d is no mask of u (1), dt (2) and grad (4)", fields);
+    if (n_p == 0) return 0;
+    STK_REQUIRE(cell && lam && t && slab && out, "stk_sample_pairs: null pointer");
+    STK_REQUIRE(M == plan->n_free, "stk_sample_pairs: a slab of %d rows on a plan of %lld free dofs", M,
+                (long long)plan->n_free);
+    STK_REQUIRE(h > 0.0 && N >= 2 && t_begin >= 0, "stk_sample_pairs: h=%g N=%d t_begin=%d", h, N, t_begin);
+    STK_REQUIRE(n_loc >= 1 && ld >= n_loc && ld_out >= n_p, "stk_sample_pairs: n_loc=%d ld=%d ld_out=%lld n_p=%lld", n_loc, ld,
+                (long long)ld_out, (long long)n_p);
+    const bool wide = !(ld & 1) && !((uintptr_t)slab & 15);
+    const double t_last = (double)(N - 1) * h;
+    const dim3 grid(stk_flat_grid(n_p, BS));
+    hipStream_t st = stk_stream(stream);
+#define STK_PAIRS(D, W)                                                                                                     \
+    hipLaunchKernelGGL((sample_pairs_kernel<D, W>), grid, dim3(BS), 0, st, n_p, plan->nc, cell, lam, t, h, t_last, N, t_begin, \
+                       n_loc, ld, slab, plan->points, plan->cells, plan->row_of, fields, ld_out, out)
+    if (plan->d == 2) {
+        if (wide) STK_PAIRS(2, true);
+        else STK_PAIRS(2, false);
+    } else {
+        if (wide) STK_PAIRS(3, true);
+        else STK_PAIRS(3, false);
+    }
+#undef STK_PAIRS
+    STK_LAUNCH_CHECK();
     return 0;
 }

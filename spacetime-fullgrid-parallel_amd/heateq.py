@@ -47,6 +47,7 @@ class HeatEquation:
         self._sample_meshes, self.sample_plan = (mesh_space, mesh_time), None
         # ... and error_norms() its plan, with the problem's exact solution if it has one
         self.error_plan, self._exact = None, (data.get('exact'), data.get('exact_grad'))
+        self.path = data.get('path')  # c(t) of a problem that follows one (--track_out), else None
         A_t, L_t, M_t, G_t, u0_t = time_matrices(mesh_time)
         M_Y, Minv_Y, B1_t, B2_t = time_matrices_test_space(mesh_time)
         M_x, A_x = space_matrices(mesh_space)
@@ -141,22 +142,40 @@ class HeatEquation:
         defect = device_vector(self.g_vec, self.N_Y) - self.B @ u
         return residual.dot(self.P @ residual), defect.dot(self.K @ defect)
 
-    def sample(self, u, times, points):
+    def sample(self, u, times, points, field='u'):
         """u_h(t_k, x_p) of a trial-space vector `u` -- the flat NumPy vector of the
         serial operators or a device vector (source.linop.device_vector) -- at `times`
         (n_k,) in [0, T] and `points` (n_p, d): an (n_k, n_p) device tensor, NaN at points
         outside the mesh.  The plan of heateq_mpi.py's sample() (source/sampling.py,
         csrc/sample.hip), built by the first call.  Test-space vectors (discontinuous in
-        time) and paired lists (t_p, x_p) are out of scope."""
+        time) are out of scope; paired lists (t_p, x_p) are served by ``sample_along``.
+        field='dt' / 'grad': the blocks of the time derivative, (n_k, n_p), and of the
+        gradient, (d, n_k, n_p)."""
+        from source.sampling import sample_collective
+        u = self._trial_vector(u)
+        return sample_collective(self.sample_plan, u, times, points, field=field)
+
+    def _trial_vector(self, u):
+        """`u` as a device vector, and the sampling plan built on first use."""
         from source.linop import _is_device_vector
-        from source.sampling import SamplePlan, sample_collective
+        from source.sampling import SamplePlan
         if not _is_device_vector(u):
             u = device_vector(u, self.N)
-        assert u.N == self.N and u.M == self.M, 'sample() takes vectors of the trial space'
+        assert u.N == self.N and u.M == self.M, 'sampling takes vectors of the trial space'
         if self.sample_plan is None:
             mesh_space, mesh_time = self._sample_meshes
             self.sample_plan = SamplePlan(mesh_space, mesh_time)
-        return sample_collective(self.sample_plan, u, times, points)
+        return u
+
+    def sample_along(self, u, times, points, fields=('u',)):
+        """u_h, its time derivative and its gradient along a trajectory: at the PAIRS
+        (times[p], points[p]) of a trial-space vector `u` -- flat NumPy vector or device
+        vector.  The dict of heateq_mpi.py's sample_along(): 'u' (n_p,), 'dt' (n_p,),
+        'grad' (d, n_p) -- those named in `fields` -- and 'inside' (n_p,), device tensors, NaN
+        outside the mesh and outside [0, T]."""
+        from source.sampling import sample_pairs_collective
+        u = self._trial_vector(u)
+        return sample_pairs_collective(self.sample_plan, u, times, points, fields)
 
     def error_norms(self, u, exact=None, exact_grad=None, times=None):
         """|| u - u_h || of a trial-space vector `u` -- flat NumPy vector or device vector
@@ -186,18 +205,21 @@ _OPTIONS = (
     ('J_space', int, 6, 'number of space refines'),
     ('precond', str, 'multigrid', 'spatial preconditioner: multigrid or direct.'),
     ('alpha', float, 0.3, 'Alpha value used in the preconditioner for X.'),
-) + driver.SAMPLE_OPTIONS  # taken off the command line again before the constructor sees it
+) + driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS  # taken off the command line before the constructor sees it
 
 
 def main(argv=None):
     parser = argparse.ArgumentParser(description='Solve the heat equation, serial wiring.')
     for flag, kind, default, text in _OPTIONS:
         parser.add_argument('--' + flag, type=kind, default=default, help=text)
-    args, sampling = driver.take_sample_options(parser.parse_args(argv))
+    args, tracking = driver.take_track_options(parser.parse_args(argv))
+    args, sampling = driver.take_sample_options(args)
     print('Arguments: %s' % args)
     print('\n\nCreating HeatEquation with %d time refines and %d space refines.'
           % (args.J_time, args.J_space))
     heat = HeatEquation(**vars(args))
+    if tracking is not None:
+        driver.require_path(heat, tracking)
     print('Size of time mesh: %d dofs. Size of space mesh: %d dofs' % (heat.N, heat.M))
     print('Solving: ', end='')
     u, iters = heat.solve(callback=lambda w, residual, k: print('.', end='', flush=True))
@@ -205,6 +227,8 @@ def main(argv=None):
           % ((iters,) + heat.errors(u)))
     if sampling is not None and sampling.sample_out:
         driver.write_samples(heat, u, sampling)
+    if tracking is not None:
+        driver.write_track(heat, u, tracking)
     if sampling is not None and sampling.error_norms:
         driver.report_error_norms(heat, u)  # this driver keeps no record: the line is the report
     return heat, u, iters

@@ -247,6 +247,7 @@ class HeatEquationMPI:
         self._sample_meshes, self.sample_plan = (mesh_space, mesh_time), None
         # ... and error_norms() its plan, with the problem's exact solution if it has one
         self.error_plan, self._exact = None, (data.get('exact'), data.get('exact_grad'))
+        self.path = data.get('path')  # c(t) of a problem that follows one (--track_out), else None
         mark('meshes')
         # the load vector and the prolongations need the mesh only: beside the
         # assembly, which runs on the host threads of libstk (no GIL held)
@@ -525,7 +526,7 @@ class HeatEquationMPI:
         defect = self.g - self.B @ u
         return residual.dot(self.P @ residual), defect.dot(self.K_Y(defect))
 
-    def sample(self, u, times, points):
+    def sample(self, u, times, points, field='u'):
         """u_h(t_k, x_p) of a trial-space vector `u` (KronVectorMPI: a solution, an iterate)
         at `times` (n_k,) in [0, T] and `points` (n_p, d) -- NumPy array, device tensor, or
         what ``sample_plan.locate`` returned -- as an (n_k, n_p) device tensor, NaN at
@@ -535,14 +536,32 @@ class HeatEquationMPI:
         the block does not depend on the number of ranks, bit for bit, and every rank
         returns all of it.  The plan (mesh and point-location grid on the device) is built
         by the first call; a run that never samples builds nothing.  Test-space vectors
-        (discontinuous in time) and paired lists (t_p, x_p) are out of scope: a paired
-        list is the diagonal of a block."""
-        from source.sampling import SamplePlan, sample_collective
-        assert u.dofs_distr.N == self.N and u.M == self.M, 'sample() takes vectors of the trial space'
+        (discontinuous in time) are out of scope; paired lists (t_p, x_p) are served by
+        ``sample_along``.  field='dt': the block of the time derivative (the right-hand one at
+        an interior node, the left-hand one at T); field='grad': the blocks of the gradient,
+        shape (d, n_k, n_p); both collective and rank-independent in the same way."""
+        from source.sampling import sample_collective
+        return sample_collective(self._sample_plan_for(u), u, times, points, field=field)
+
+    def _sample_plan_for(self, u):
+        from source.sampling import SamplePlan
+        assert u.dofs_distr.N == self.N and u.M == self.M, 'sampling takes vectors of the trial space'
         if self.sample_plan is None:
             mesh_space, mesh_time = self._sample_meshes
             self.sample_plan = SamplePlan(mesh_space, mesh_time)
-        return sample_collective(self.sample_plan, u, times, points)
+        return self.sample_plan
+
+    def sample_along(self, u, times, points, fields=('u',)):
+        """u_h, its time derivative and its gradient of a trial-space vector `u` along a
+        trajectory: at the PAIRS (times[p], points[p]), `times` (n_p,) and `points` (n_p, d)
+        NumPy arrays or device tensors.  Returns a dict of device tensors: 'u' (n_p,),
+        'dt' (n_p,), 'grad' (d, n_p) -- those named in `fields` -- and 'inside' (n_p,) bool;
+        NaN where a point is outside the mesh or a time is NaN or outside [0, T] (checked on
+        the device).  The work is 2 (d + 1) slab entries per point, never the (n_p, n_p)
+        block.  COLLECTIVE and independent of the number of ranks, bit for bit, as
+        ``sample``; the plan is built by the first call of either."""
+        from source.sampling import sample_pairs_collective
+        return sample_pairs_collective(self._sample_plan_for(u), u, times, points, fields)
 
     def error_norms(self, u, exact=None, exact_grad=None, times=None):
         """|| u - u_h || of a trial-space vector `u` (KronVectorMPI) against `exact`
@@ -583,10 +602,13 @@ def main(argv=None):
                                 'reference\'s arithmetic (r.Pr history within 1e-10 of the CPU '
                                 'path); fast: both regrouped everywhere (4 %% less solve time, history '
                                 'within 4.6e-10); reference: every regrouping of the build off '
-                                '(2.3x slower than fast)')] + list(driver.SAMPLE_OPTIONS))
+                                '(2.3x slower than fast)')] + list(driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS))
+    args, tracking = driver.take_track_options(args)
     args, sampling = driver.take_sample_options(args)
     comm, rank, size = driver.start(args)
     heat = HeatEquationMPI(**driver.solver_arguments(args))
+    if tracking is not None:
+        driver.require_path(heat, tracking)
     # per-rank record, gathered and printed as one blob at the end
     record = {'rank': rank, 'mem_after_construction': mem()}
     if size > 1:
@@ -644,6 +666,8 @@ def main(argv=None):
                   % (iters, error_alg, error_Yprime))
     if sampling is not None and sampling.sample_out:
         driver.write_samples(heat, solution, sampling, rank)  # collective
+    if tracking is not None:
+        driver.write_track(heat, solution, tracking, rank)  # collective
     if sampling is not None and sampling.error_norms:
         norms = driver.report_error_norms(heat, solution, rank)  # collective
         if norms is not None:

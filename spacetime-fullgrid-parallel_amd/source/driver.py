@@ -33,6 +33,12 @@ SAMPLE_OPTIONS = (
     ('error_norms', int, 0, '1: after the solve, the L2(L2), L2(H1) and final-time L2 norms of the error against'
      ' the exact solution of the problem, by quadrature on the device'),
 )
+# ... and for following the problem's path (data['path']) through the solution
+TRACK_OPTIONS = (
+    ('track_out', str, None, 'write the solution, its time derivative and its gradient along the path of the'
+     ' problem (e.g. under the moving source) to this .npz'),
+    ('track_points', int, 1025, 'number of equally spaced times from 0 to T along the path'),
+)
 
 
 def device_mb():
@@ -126,6 +132,13 @@ def take_sample_options(args):
     return args, (sampling if sampling.sample_out or sampling.error_norms else None)
 
 
+def take_track_options(args):
+    """(the parsed command line without the tracking options, those options or None
+    without --track_out)."""
+    tracking = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in TRACK_OPTIONS})
+    return args, (tracking if tracking.track_out else None)
+
+
 def report_error_norms(heat, solution, rank=0):
     """--error_norms: one line with the four norms of u - u_h and the relative errors
     (heat.error_norms, collective; works for both solve drivers), and the dict for the
@@ -162,6 +175,32 @@ def write_samples(heat, solution, args, rank=0):
             np.savez(f, times=times, points=points, inside=located.inside.cpu().numpy(),
                      values=values.cpu().numpy())
     return values
+
+
+def require_path(heat, args):
+    """Ends the run with a message where --track_out cannot be served: the drivers ask
+    before they solve."""
+    if getattr(heat, 'path', None) is None:
+        raise SystemExit('--track_out: this problem has no path to follow (square_moving_source has one)')
+    if args.track_points < 1:
+        raise SystemExit('--track_points must be at least 1')
+
+
+def write_track(heat, solution, args, rank=0):
+    """--track_out: u_h, d/dt u_h and grad u_h along the path c(t) of the problem
+    (heat.path = data['path']) at track_points equally spaced times from 0 to T, written by
+    rank 0 as an .npz with times (K,), points (K, d), inside (K,), u (K,), dt (K,) and grad
+    (d, K).  Collective (heat.sample_along); works for both solve drivers."""
+    require_path(heat, args)
+    _, mesh_time = heat._sample_meshes
+    times = np.linspace(0.0, mesh_time.T, args.track_points)
+    points = np.ascontiguousarray(np.asarray(heat.path(times), dtype=np.float64))
+    assert points.ndim == 2 and points.shape[0] == len(times), points.shape
+    got = heat.sample_along(solution, times, points, fields=('u', 'dt', 'grad'))
+    if rank == 0:
+        with open(args.track_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
+            np.savez(f, times=times, points=points, **{k: got[k].cpu().numpy() for k in ('inside', 'u', 'dt', 'grad')})
+    return got
 
 
 def publish(comm, record):

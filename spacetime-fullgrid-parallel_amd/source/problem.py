@@ -31,7 +31,8 @@ as well, which is what the tests and ``exact`` use.
     g = E [(d pi^2 - (1 + x) - t^2) s + 2 t pi cos(pi x) sin(pi y) [sin(pi z)]],  u(0) = s.
 ``square_moving_source``: u(0) = 0 and a Gaussian heat source of width 0.1 on a circle,
     g = exp(-|x - c(t)|^2 / (2 0.1^2)),  c(t) = (0.5 + 0.25 cos 2 pi t, 0.5 + 0.25 sin 2 pi t);
-no exact solution.
+no exact solution; ``data['path']`` is the callable c(t) (times (K,) -> points (K, 2)) that
+the drivers' --track_out follows.
 """
 import sys
 
@@ -209,17 +210,27 @@ def cube_nonseparable(J_space, J_time=None):
     return mesh_space, bc, _time_mesh(J_space, J_time), _nonseparable_data(3), "cube_nonseparable"
 
 
+def _moving_source_centre(xp, t):
+    return 0.5 + 0.25 * xp.cos(2.0 * np.pi * t), 0.5 + 0.25 * xp.sin(2.0 * np.pi * t)
+
+
 def _moving_source(t, x, y):
     xp = _array_module(t, x, y)
     t, x, y = _as_array(xp, t), _as_array(xp, x), _as_array(xp, y)
-    cx = 0.5 + 0.25 * xp.cos(2.0 * np.pi * t)
-    cy = 0.5 + 0.25 * xp.sin(2.0 * np.pi * t)
+    cx, cy = _moving_source_centre(xp, t)
     return xp.exp(-((x - cx)**2 + (y - cy)**2) / (2.0 * 0.1**2))
+
+
+def _moving_source_path(t):
+    """c(t), the centre of the source: times (K,) -> points (K, 2), NumPy arrays or torch
+    tensors."""
+    xp = _array_module(t)
+    return xp.stack(_moving_source_centre(xp, _as_array(xp, t)), -1)
 
 
 def square_moving_source(J_space, J_time=None):
     mesh_space, bc = construct_2d_square_mesh(nrefines=J_space)
-    data = {'g': [_moving_source], 'u0': lambda x, y: np.zeros_like(x)}
+    data = {'g': [_moving_source], 'u0': lambda x, y: np.zeros_like(x), 'path': _moving_source_path}
     return mesh_space, bc, _time_mesh(J_space, J_time), data, "square_moving_source"
 
 

@@ -13,9 +13,13 @@ rasters of time slices, probes at points, cuts along lines.
 * ``raster``: a regular grid of points over the bounding box (pure NumPy).
 * ``bucket_grid``: the point-location grid as host arrays (no GPU needed).
 
-Scope: vectors of the TRIAL space (continuous piecewise linear in time) and the full
-points x times block.  Test-space vectors (discontinuous in time) and paired lists
-(t_p, x_p) are not served; a paired list is the diagonal of a block.
+* ``evaluate_pairs(vec, times, located, fields)``: paired lists (t_p, x_p) -- a
+  trajectory, a set of tracers -- without the block they are the diagonal of, and with
+  the derivatives: u_h, d/dt u_h and grad u_h per point (stk_sample_pairs).  The block
+  forms of the derivatives are ``evaluate(..., field='dt' | 'grad')``.
+
+Scope: vectors of the TRIAL space (continuous piecewise linear in time).  Test-space
+vectors (discontinuous in time) and second derivatives are not served.
 """
 import ctypes
 
@@ -141,21 +145,60 @@ class SamplePlan:
                                                     _lib.ptr(lam)))
         return Located(cell, lam)
 
-    def evaluate(self, vec, times, located, out=None):
-        """This rank's contribution to u_h(t_k, x_p) of the trial-space vector `vec`
-        (KronVectorMPI), shape (n_k, n_p): the terms of the time nodes this rank owns,
-        exactly 0.0 for the others, NaN at points outside the mesh.  The sum over the
-        ranks is the value (HeatEquationMPI.sample all-reduces it)."""
-        import torch
-        _lib = self._lib
+    def _time_mesh_of(self, vec):
         mesh_time = self.mesh_time
         if mesh_time is None:
             from .mesh import construct_interval
             mesh_time = construct_interval(N=vec.N - 1)
         assert mesh_time.nv == vec.N, (mesh_time.nv, vec.N)
         assert vec.M == self.n_free, (vec.M, self.n_free)
+        return mesh_time
+
+    def grad_coeffs(self, located):
+        """(d, n_p, d + 1) device tensor: [j, p, a] = d_j lambda_a of the cell of point p
+        (stk_sample_grad_coeffs), NaN for a point outside the mesh."""
+        import torch
+        _lib = self._lib
+        out = torch.empty((self.d, located.n_p, self.d + 1), dtype=torch.float64, device=located.cell.device)
+        if located.n_p:
+            _lib.check(_lib.lib().stk_sample_grad_coeffs(_lib.stream(), self._plan, located.n_p, _lib.ptr(located.cell),
+                                                         _lib.ptr(out)))
+        return out
+
+    def evaluate(self, vec, times, located, out=None, field='u'):
+        """This rank's contribution to u_h(t_k, x_p) of the trial-space vector `vec`
+        (KronVectorMPI), shape (n_k, n_p): the terms of the time nodes this rank owns,
+        exactly 0.0 for the others, NaN at points outside the mesh.  The sum over the
+        ranks is the value (HeatEquationMPI.sample all-reduces it).
+
+        field='dt': the block of d/dt u_h, the same kernel with the weights (-1/h, 1/h)
+        (the right-hand derivative at an interior node, the left-hand one at T);
+        field='grad': the blocks of grad u_h, shape (d, n_k, n_p), the same kernel with
+        the rows of ``grad_coeffs`` in place of the barycentric coordinates."""
+        import torch
+        _lib = self._lib
+        if field not in FIELDS:
+            raise ValueError('field must be one of %s, not %r' % (FIELDS, field))
+        mesh_time = self._time_mesh_of(vec)
         columns, weights = time_weights(mesh_time, times, vec.t_begin, vec.t_end)
         n_k, n_p = len(columns), located.n_p
+        if field != 'u':
+            if field == 'dt':
+                weights = np.ascontiguousarray(np.broadcast_to(np.array([-1.0, 1.0]) / mesh_time.h, columns.shape))
+                lams = [located.lam]
+            else:
+                lams = list(self.grad_coeffs(located))
+            shape = (len(lams), n_k, n_p)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float64, device=vec.buf.device)
+            assert tuple(out.reshape(shape).shape) == shape and out.is_contiguous() and out.dtype == torch.float64
+            if n_k and n_p:
+                for j, lam in enumerate(lams):
+                    _lib.check(_lib.lib().stk_sample_eval(
+                        _lib.stream(), self._plan, n_p, _lib.ptr(located.cell), _lib.ptr(lam), vec.M, vec.n_loc, vec.ld,
+                        _lib.ptr(vec.buf), n_k, columns.ctypes.data, weights.ctypes.data, n_p,
+                        _lib.ptr(out.reshape(shape)[j])))
+            return out.reshape(shape[1:]) if field == 'dt' else out
         if out is None:
             out = torch.empty((n_k, n_p), dtype=torch.float64, device=vec.buf.device)
         assert tuple(out.shape) == (n_k, n_p) and out.is_contiguous() and out.dtype == torch.float64
@@ -165,12 +208,81 @@ class SamplePlan:
                 _lib.ptr(vec.buf), n_k, columns.ctypes.data, weights.ctypes.data, n_p, _lib.ptr(out)))
         return out
 
+    def _pair_rows(self, vec, times, located, fields):
+        """(mask, rows): the (n_rows, n_p) device tensor stk_sample_pairs fills, rows in
+        the order u, dt, grad_0 .. grad_(d-1), the requested ones only."""
+        import torch
+        _lib = self._lib
+        mask = field_mask(fields)
+        mesh_time = self._time_mesh_of(vec)
+        dev = vec.buf.device
+        if not torch.is_tensor(times):
+            times = torch.from_numpy(np.array(times, dtype=np.float64, order='C'))  # a copy: torch wants it writable
+        times = times.to(device=dev, dtype=torch.float64).contiguous()
+        n_p = located.n_p
+        assert tuple(times.shape) == (n_p,), (tuple(times.shape), n_p)
+        n_rows = (mask & 1) + (mask >> 1 & 1) + (mask >> 2 & 1) * self.d
+        rows = torch.empty((n_rows, n_p), dtype=torch.float64, device=dev)
+        if n_p:
+            _lib.check(_lib.lib().stk_sample_pairs(
+                _lib.stream(), self._plan, n_p, _lib.ptr(located.cell), _lib.ptr(located.lam), _lib.ptr(times),
+                float(mesh_time.h), vec.N, vec.t_begin, vec.M, vec.n_loc, vec.ld, _lib.ptr(vec.buf), mask, n_p,
+                _lib.ptr(rows)))
+        return mask, rows
 
-def sample_collective(plan, vec, times, points):
+    def _split_rows(self, mask, rows):
+        out, at = {}, 0
+        if mask & 1:
+            out['u'], at = rows[at], at + 1
+        if mask & 2:
+            out['dt'], at = rows[at], at + 1
+        if mask & 4:
+            out['grad'] = rows[at:at + self.d]
+        return out
+
+    def evaluate_pairs(self, vec, times, located, fields=('u',)):
+        """This rank's contributions at the PAIRS (times[p], point p) -- one time per
+        located point, `times` a NumPy array or device tensor of shape (n_p,) -- as a dict
+        of device tensors: 'u' (n_p,), 'dt' (n_p,), 'grad' (d, n_p), those named in
+        `fields`.  The terms of the time nodes this rank owns, exactly 0.0 for the others;
+        NaN where the point is outside the mesh or the time is NaN or outside [0, T] (checked
+        on the device: nothing here waits for it).  The sum over the ranks is the value."""
+        return self._split_rows(*self._pair_rows(vec, times, located, fields))
+
+
+FIELDS = ('u', 'dt', 'grad')
+
+
+def field_mask(fields):
+    """The bit mask of stk_sample_pairs (1 = u, 2 = dt, 4 = grad) of a field name or a
+    sequence of names."""
+    names = (fields,) if isinstance(fields, str) else tuple(fields)
+    if not names or any(f not in FIELDS for f in names):
+        raise ValueError('fields must name some of %s, not %r' % (FIELDS, fields))
+    return sum(1 << FIELDS.index(f) for f in set(names))
+
+
+def sample_collective(plan, vec, times, points, field='u'):
     """The full (n_k, n_p) block on every rank: the local contributions all-reduced with
     the communicator of the vector, the pattern of KronVectorMPI.dot -- every term has
     exactly one non-zero contributor, so the block is the one-rank block bit for bit
-    whatever the rank count."""
-    block = plan.evaluate(vec, times, plan.locate(points))
+    whatever the rank count.  field='dt' / 'grad': the blocks of the derivatives
+    ((n_k, n_p) / (d, n_k, n_p)), in the same way."""
+    block = plan.evaluate(vec, times, plan.locate(points), field=field)
     vec.dofs_distr.comm.allreduce_tensor_(block)
     return block
+
+
+def sample_pairs_collective(plan, vec, times, points, fields=('u',)):
+    """The pairs (times[p], points[p]) on every rank: dict with 'u' (n_p,), 'dt' (n_p,),
+    'grad' (d, n_p) -- those named in `fields` -- and 'inside' (n_p,) bool.  The local rows
+    are all-reduced in one call; every term has exactly one non-zero contributor (the
+    owner of its time node), so every entry is the one-rank double whatever the rank
+    count."""
+    located = plan.locate(points)
+    mask, rows = plan._pair_rows(vec, times, located, fields)
+    if rows.numel():
+        vec.dofs_distr.comm.allreduce_tensor_(rows)
+    out = plan._split_rows(mask, rows)
+    out['inside'] = located.inside
+    return out
