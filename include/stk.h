@@ -1181,7 +1181,45 @@ int stk_load_columns(void *stream, const stk_load_plan *plan, int32_t nq,
  * each quotient rounded once.  stk_sample_grad_coeffs writes the same doubles per located
  * point, out [d][n_p][d + 1] (DEVICE; out[j][p][a] = d_j l_a, NaN for cell < 0): row j,
  * passed to stk_sample_eval as `lam`, gives the (n_k, n_p) block of grad_j, and
- * stk_sample_eval with the weights (-1 / h, 1 / h) gives the block of dt. */
+ * stk_sample_eval with the weights (-1 / h, 1 / h) gives the block of dt.
+ *
+ * THE ADJOINT OF PAIRED SAMPLING.  stk_sample_pairs_adjoint applies E^T: numbers w_p given
+ * at the pairs (t_p, x_p) become the functional v -> sum_p w_p v_h(t_p, x_p) (field 1 = u),
+ * sum_p w_p d/dt v_h (field 2 = dt) or sum_p w_p . grad v_h (field 4 = grad) on the trial
+ * space, written into a slab -- the right-hand side of a solve that uses measurements.  It
+ * takes what stk_sample_pairs takes (cell, lam, t, h, N, t_begin, M, n_loc, ld; the slab is
+ * now the OUTPUT), DEVICE weights w [n_w][ld_w >= n_p] (n_w = 1 for u and dt, n_w = d for
+ * grad), `field` (exactly one of 1, 2, 4), `accumulate` (0 or 1), a DEVICE byte array
+ * used [n_p] and a DEVICE workspace of stk_sample_pairs_adjoint_work_size(n_p, d, &bytes)
+ * bytes on a 256-byte boundary (the size query asks the sort for its scratch, which looks
+ * at the current device).  The call allocates nothing and does not synchronise.
+ *
+ * Point p is USED when cell >= 0, t is not NaN and 0 <= t <= (N - 1) h, decided on the
+ * device; used[p] = 1 then, else 0, and an unused point contributes nothing (its weight and
+ * coordinates are not looked at: a NaN there poisons nothing).  For a used point e, s and
+ * (w_0, w_1) = (1 - s, s) are those of stk_sample_pairs and G_j[b] = d_j l_b the doubles of
+ * stk_sample_grad_coeffs.  Its terms, for a = 0, 1 and local vertex b = 0 .. d:
+ *     u      (w[p] w_a) lam[p][b]
+ *     dt     (-(w[p] / h)) lam[p][b] for a = 0,   (w[p] / h) lam[p][b] for a = 1
+ *     grad   w_a q_b,   q_b = ((w[0][p] G_0[b] + w[1][p] G_1[b]) [+ w[2][p] G_2[b]])
+ * every product, quotient and sum rounded on its own (no fused multiply-adds).  The term
+ * goes to the local column e + a - t_begin if that lies in [0, n_loc) and to the slab row
+ * of vertex v_b if that vertex is free; any other term is dropped.
+ *
+ * An entry's terms are taken in ascending p (for one p: a, then b) and cut into chunks of
+ * STK_SAMPLE_ADJ_CHUNK consecutive terms; each chunk is summed from the left starting with
+ * its first term, and the chunk sums are added from the left in chunk order (for up to
+ * STK_SAMPLE_ADJ_CHUNK terms: the plain sum from the left).  accumulate = 0: every entry of
+ * the n_loc valid columns becomes that sum, +0.0 where no term lands; accumulate = 1:
+ * old + sum at the entries with terms, the others untouched.  The padding column of an odd
+ * n_loc is never written.  No float atomics: one lane per point stores its 2 (d + 1)
+ * (64-bit destination, term) records, a stable sort groups them by destination and keeps
+ * ascending p, and one pass sums every run by the rule above -- so a slab entry does not
+ * depend on the launch shape, nor on the number of ranks: every rank is given ALL pairs and
+ * builds the entries of the columns it owns, without communication.  n_p = 0 is the zero
+ * fill alone.  One call indexes 2 (d + 1) n_p < 2^31 records; more is refused (return 2,
+ * also by the size query): split the list and accumulate. */
+#define STK_SAMPLE_ADJ_CHUNK 512
 typedef struct stk_sample_grid stk_sample_grid;
 typedef struct stk_sample_plan stk_sample_plan;
 int stk_sample_grid_build(int32_t d, int64_t nv, int64_t nc, const double *points,
@@ -1207,6 +1245,13 @@ int stk_sample_pairs(void *stream, const stk_sample_plan *plan, int64_t n_p,
                      const double *slab, int32_t fields, int64_t ld_out, double *out);
 int stk_sample_grad_coeffs(void *stream, const stk_sample_plan *plan, int64_t n_p,
                            const int32_t *cell, double *out);
+int stk_sample_pairs_adjoint_work_size(int64_t n_p, int32_t d, int64_t *bytes);
+int stk_sample_pairs_adjoint(void *stream, const stk_sample_plan *plan, int64_t n_p,
+                             const int32_t *cell, const double *lam, const double *t,
+                             double h, int32_t N, int32_t t_begin, int32_t M, int32_t n_loc,
+                             int32_t ld, double *slab, const double *w, int64_t ld_w,
+                             int32_t field, int32_t accumulate, unsigned char *used,
+                             void *work, int64_t work_bytes);
 
 /* ---- space-time error norms: || u - u_h || by quadrature on the device --------------
  * The error of a trial-space vector (continuous P1 in time on a uniform mesh, P1 on a

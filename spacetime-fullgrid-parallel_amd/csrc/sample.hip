@@ -15,6 +15,9 @@
 //                           derivative and its gradient from 2 (d + 1) slab entries
 //  * stk_sample_grad_coeffs the gradients of the barycentric coordinates per located point:
 //                           as `lam` of stk_sample_eval they give the blocks of the gradient
+//  * stk_sample_pairs_adjoint  E^T of the pairs: numbers at (t_p, x_p) onto the slab, as
+//                           store, stable sort by destination (sample_adj_sort.hip) and one
+//                           summing pass -- no float atomics, one order per entry
 //
 // THE EVAL KERNEL.  A slab row is contiguous in time and a point needs d + 1 whole rows, so
 // the pass is a row gather, and its output is time-major: points x times turned through
@@ -36,6 +39,7 @@
 #include <thread>
 #include <vector>
 
+#include "sample_adj_sort.h"
 #include "stk_common.h"
 
 #pragma clang fp contract(off)
@@ -443,6 +447,176 @@ __global__ __launch_bounds__(BS) void sample_pairs_kernel(int64_t n_p, int64_t n
     }
 }
 
+// ---- the adjoint of the pairs kernel: store, group, sum -----------------------------------
+// E^T w as the store-and-sum form of a scatter-add: no float atomics, one fixed order per
+// entry.  (1) One lane per point writes its 2 (D + 1) records (destination key, term) at
+// p K + a (D + 1) + b, K = 2 (D + 1): ascending p, then a, then b.  The key of a kept term is
+// row n_loc + column (64-bit); a dropped term -- an unused point, a column of another rank,
+// a boundary vertex -- gets the key M n_loc, one past the last entry, and sorts behind them
+// all.  (2) A stable sort by key (sample_adj_sort.hip) makes every entry's terms a run in
+// that order.  (3) The run is cut into chunks of STK_SAMPLE_ADJ_CHUNK terms from its start;
+// the lane AT the first record of a chunk sums it from the left.  A run of one chunk is
+// stored at once; the chunk sums of a longer one are parked on the chunk's first record and
+// added from the left, by the lane at the run's start, in a second launch.  Which lane sums
+// what depends on the sorted records alone, never on the launch shape.
+constexpr int ADJ_CHUNK = STK_SAMPLE_ADJ_CHUNK;
+
+template <int D>
+__global__ __launch_bounds__(BS) void sample_adj_records_kernel(
+    int64_t n_p, int64_t nc, const int32_t *__restrict__ cell, const double *__restrict__ lam, const double *__restrict__ t,
+    double h, double t_last, int32_t N, int32_t t_begin, int32_t n_loc, uint64_t none, const double *__restrict__ w,
+    int64_t ld_w, int32_t field, const double *__restrict__ pts, const int32_t *__restrict__ cells,
+    const int32_t *__restrict__ row_of, uint64_t *__restrict__ keys, double *__restrict__ vals,
+    unsigned char *__restrict__ used)
+{
+    constexpr int K = 2 * (D + 1);
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    for (int64_t p = (int64_t)blockIdx.x * BS + threadIdx.x; p < n_p; p += stride) {
+        const int32_t tc = cell[p];
+        const double tp = t[p];
+        const bool ok = tc >= 0 && tc < nc && tp >= 0.0 && tp <= t_last;  // a NaN time fails both comparisons
+        uint64_t key[K];
+        double term[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) key[k] = none, term[k] = 0.0;
+        if (ok) {
+            const double x = tp / h;
+            double ef = floor(x);
+            if (ef > (double)(N - 2)) ef = (double)(N - 2);
+            const double w1 = x - ef, w0 = 1.0 - w1;
+            const int64_t c0 = (int64_t)ef - t_begin, c1 = c0 + 1;
+            const bool have0 = c0 >= 0 && c0 < n_loc, have1 = c1 >= 0 && c1 < n_loc;
+            int32_t v[D + 1];
+#pragma unroll
+            for (int b = 0; b <= D; ++b) v[b] = cells[(D + 1) * (int64_t)tc + b];
+            if (field == 4) {
+                double G[D + 1][D], wj[D];
+                barycentric_gradients<D>(pts, v, G);
+#pragma unroll
+                for (int j = 0; j < D; ++j) wj[j] = w[j * ld_w + p];
+#pragma unroll
+                for (int b = 0; b <= D; ++b) {
+                    double q = wj[0] * G[b][0];
+#pragma unroll
+                    for (int j = 1; j < D; ++j) q = q + wj[j] * G[b][j];
+                    term[b] = w0 * q, term[D + 1 + b] = w1 * q;
+                }
+            } else {
+                const double wp = w[p];
+                double k0, k1;
+                if (field == 1) {
+                    k0 = wp * w0, k1 = wp * w1;
+                } else {
+                    k1 = wp / h, k0 = -k1;
+                }
+#pragma unroll
+                for (int b = 0; b <= D; ++b) {
+                    const double l = lam[(D + 1) * p + b];
+                    term[b] = k0 * l, term[D + 1 + b] = k1 * l;
+                }
+            }
+#pragma unroll
+            for (int b = 0; b <= D; ++b) {
+                const int32_t r = row_of[v[b]];
+                if (r >= 0 && have0) key[b] = (uint64_t)r * (uint64_t)n_loc + (uint64_t)c0;
+                if (r >= 0 && have1) key[D + 1 + b] = (uint64_t)r * (uint64_t)n_loc + (uint64_t)c1;
+            }
+        }
+        used[p] = ok ? 1 : 0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) keys[K * p + k] = key[k], vals[K * p + k] = term[k];
+    }
+}
+
+// every valid column +0.0; the padding column of an odd n_loc is not touched
+__global__ __launch_bounds__(BS) void sample_adj_zero_kernel(int64_t entries, int32_t n_loc, int32_t ld,
+                                                             double *__restrict__ out)
+{
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < entries; i += stride) {
+        const int64_t row = i / n_loc;
+        out[row * ld + (i - row * n_loc)] = 0.0;
+    }
+}
+
+__device__ inline void adj_store(uint64_t key, double sum, int32_t n_loc, int32_t ld, int32_t accumulate,
+                                 double *__restrict__ out)
+{
+    const uint64_t row = key / (uint64_t)n_loc;
+    double *at = out + (int64_t)row * ld + (int64_t)(key - row * (uint64_t)n_loc);
+    *at = accumulate ? *at + sum : sum;
+}
+
+// one lane per sorted record; works where the record opens a chunk of its run
+__global__ __launch_bounds__(BS) void sample_adj_chunks_kernel(int64_t n, uint64_t none,
+                                                               const uint64_t *__restrict__ keys, double *vals,
+                                                               int32_t n_loc, int32_t ld, int32_t accumulate,
+                                                               double *__restrict__ out)
+{
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += stride) {
+        const uint64_t k = keys[i];
+        if (k >= none) continue;
+        const bool opens_run = i == 0 || keys[i - 1] != k;
+        bool opens_chunk = opens_run;
+        if (!opens_run && i >= ADJ_CHUNK && keys[i - ADJ_CHUNK] == k) {
+            // ADJ_CHUNK or more records of this run lie before i: find its start, the first
+            // record whose key is not below k
+            int64_t lo = 0, hi = i - ADJ_CHUNK;  // keys[hi] == k
+            while (lo < hi) {
+                const int64_t mid = lo + (hi - lo) / 2;
+                if (keys[mid] < k) lo = mid + 1;
+                else hi = mid;
+            }
+            opens_chunk = (i - lo) % ADJ_CHUNK == 0;
+        }
+        if (!opens_chunk) continue;
+        double sum = vals[i];
+        int64_t j = i + 1;
+        const int64_t end = i + ADJ_CHUNK < n ? i + ADJ_CHUNK : n;
+        for (; j < end && keys[j] == k; ++j) sum = sum + vals[j];
+        const bool more = j == i + ADJ_CHUNK && j < n && keys[j] == k;
+        if (opens_run && !more) adj_store(k, sum, n_loc, ld, accumulate, out);
+        else vals[i] = sum;  // read by this lane alone in this launch
+    }
+}
+
+// the runs of more than one chunk: the parked chunk sums, added from the left
+__global__ __launch_bounds__(BS) void sample_adj_runs_kernel(int64_t n, uint64_t none,
+                                                             const uint64_t *__restrict__ keys,
+                                                             const double *__restrict__ vals, int32_t n_loc, int32_t ld,
+                                                             int32_t accumulate, double *__restrict__ out)
+{
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i + ADJ_CHUNK < n; i += stride) {
+        const uint64_t k = keys[i];
+        if (k >= none || keys[i + ADJ_CHUNK] != k || (i > 0 && keys[i - 1] == k)) continue;
+        double total = vals[i];
+        for (int64_t j = i + ADJ_CHUNK; j < n && keys[j] == k; j += ADJ_CHUNK) total = total + vals[j];
+        adj_store(k, total, n_loc, ld, accumulate, out);
+    }
+}
+
+inline size_t adj_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// workspace: keys [2][n_rec] (uint64), terms [2][n_rec] (double), the sort's scratch; every
+// part on a 256-byte boundary
+int adj_layout(int64_t n_p, int32_t d, size_t *part, size_t *sort_bytes, size_t *total)
+{
+    STK_REQUIRE(n_p >= 0 && (d == 2 || d == 3), "stk_sample_pairs_adjoint: n_p=%lld d=%d", (long long)n_p, d);
+    STK_REQUIRE(n_p <= (((int64_t)1 << 31) - 1) / (2 * (d + 1)),
+                "stk_sample_pairs_adjoint: %lld points are 2 (d + 1) n_p >= 2^31 records, more than one call indexes; "
+                "split the list and accumulate",
+                (long long)n_p);
+    const int64_t n_rec = 2 * (int64_t)(d + 1) * n_p;
+    *part = adj_align((size_t)n_rec * 8);
+    *sort_bytes = 0;
+    if (n_rec)
+        if (int rc = stk_adj_sort_temp_bytes(n_rec, sort_bytes)) return rc;
+    *total = 4 * *part + adj_align(*sort_bytes);
+    return 0;
+}
+
 template <typename T>
 int upload(T **dst, const T *src, size_t n)
 {
@@ -806,5 +980,74 @@ extern "C" int stk_sample_pairs(void *stream, const stk_sample_plan *plan, int64
     }
 #undef STK_PAIRS
     STK_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int stk_sample_pairs_adjoint_work_size(int64_t n_p, int32_t d, int64_t *bytes)
+{
+    STK_REQUIRE(bytes, "stk_sample_pairs_adjoint_work_size: null pointer");
+    size_t part, sort_bytes, total;
+    if (int rc = adj_layout(n_p, d, &part, &sort_bytes, &total)) return rc;
+    *bytes = (int64_t)total;
+    return 0;
+}
+
+extern "C" int stk_sample_pairs_adjoint(void *stream, const stk_sample_plan *plan, int64_t n_p, const int32_t *cell,
+                                        const double *lam, const double *t, double h, int32_t N, int32_t t_begin, int32_t M,
+                                        int32_t n_loc, int32_t ld, double *slab, const double *w, int64_t ld_w, int32_t field,
+                                        int32_t accumulate, unsigned char *used, void *work, int64_t work_bytes)
+{
+    const stk_timed timed_(STK_OP_SPACE, stream);
+    STK_REQUIRE(plan && n_p >= 0 && slab, "stk_sample_pairs_adjoint: bad arguments");
+    STK_REQUIRE(field == 1 || field == 2 || field == 4, "stk_sample_pairs_adjoint: field=%d is none of u (1), dt (2), grad (4)",
+                field);
+    STK_REQUIRE(accumulate == 0 || accumulate == 1, "stk_sample_pairs_adjoint: accumulate=%d", accumulate);
+    STK_REQUIRE(M == plan->n_free, "stk_sample_pairs_adjoint: a slab of %d rows on a plan of %lld free dofs", M,
+                (long long)plan->n_free);
+    STK_REQUIRE(h > 0.0 && N >= 2 && t_begin >= 0, "stk_sample_pairs_adjoint: h=%g N=%d t_begin=%d", h, N, t_begin);
+    STK_REQUIRE(n_loc >= 1 && ld >= n_loc && ld_w >= n_p, "stk_sample_pairs_adjoint: n_loc=%d ld=%d ld_w=%lld n_p=%lld", n_loc,
+                ld, (long long)ld_w, (long long)n_p);
+    size_t part, sort_bytes, total;
+    if (int rc = adj_layout(n_p, plan->d, &part, &sort_bytes, &total)) return rc;
+    if (n_p > 0) {
+        STK_REQUIRE(cell && lam && t && w && used && work, "stk_sample_pairs_adjoint: null pointer");
+        STK_REQUIRE(!((uintptr_t)work & 255) && work_bytes >= (int64_t)total,
+                    "stk_sample_pairs_adjoint: a workspace of %lld bytes at %p; %lld on a 256-byte boundary are needed",
+                    (long long)work_bytes, work, (long long)total);
+    }
+    hipStream_t st = stk_stream(stream);
+    const int64_t entries = (int64_t)M * n_loc;
+    if (!accumulate) {
+        hipLaunchKernelGGL(sample_adj_zero_kernel, dim3(stk_flat_grid(entries, BS)), dim3(BS), 0, st, entries, n_loc, ld, slab);
+        STK_LAUNCH_CHECK();
+    }
+    if (n_p == 0) return 0;
+    char *base = static_cast<char *>(work);
+    uint64_t *const keys[2] = {reinterpret_cast<uint64_t *>(base), reinterpret_cast<uint64_t *>(base + part)};
+    double *const vals[2] = {reinterpret_cast<double *>(base + 2 * part), reinterpret_cast<double *>(base + 3 * part)};
+    const int64_t n_rec = 2 * (int64_t)(plan->d + 1) * n_p;
+    const uint64_t none = (uint64_t)entries;  // the key of a dropped term: one past the last entry
+    int key_bits = 1;
+    while (key_bits < 64 && (none >> key_bits)) ++key_bits;
+    const double t_last = (double)(N - 1) * h;
+    const dim3 grid(stk_flat_grid(n_p, BS));
+    if (plan->d == 2)
+        hipLaunchKernelGGL(sample_adj_records_kernel<2>, grid, dim3(BS), 0, st, n_p, plan->nc, cell, lam, t, h, t_last, N, t_begin,
+                           n_loc, none, w, ld_w, field, plan->points, plan->cells, plan->row_of, keys[0], vals[0], used);
+    else
+        hipLaunchKernelGGL(sample_adj_records_kernel<3>, grid, dim3(BS), 0, st, n_p, plan->nc, cell, lam, t, h, t_last, N, t_begin,
+                           n_loc, none, w, ld_w, field, plan->points, plan->cells, plan->row_of, keys[0], vals[0], used);
+    STK_LAUNCH_CHECK();
+    int half = 0;
+    if (int rc = stk_adj_sort(st, base + 4 * part, adj_align(sort_bytes), keys, vals, n_rec, key_bits, &half)) return rc;
+    const dim3 grid_rec(stk_flat_grid(n_rec, BS));
+    hipLaunchKernelGGL(sample_adj_chunks_kernel, grid_rec, dim3(BS), 0, st, n_rec, none, keys[half], vals[half], n_loc, ld,
+                       accumulate, slab);
+    STK_LAUNCH_CHECK();
+    if (n_rec > ADJ_CHUNK) {
+        hipLaunchKernelGGL(sample_adj_runs_kernel, grid_rec, dim3(BS), 0, st, n_rec, none, keys[half], vals[half], n_loc, ld,
+                           accumulate, slab);
+        STK_LAUNCH_CHECK();
+    }
     return 0;
 }

@@ -120,18 +120,28 @@ class HeatEquation:
         self.u0_x = space_load(mesh_space, data['u0'])
         self.f = self.BT @ (self.K @ self.g_vec) + np.kron(u0_t, self.u0_x)
 
-    def solve(self, callback=None, on_host=False):
+    def solve(self, callback=None, on_host=False, rhs=None):
         """PCG on the wavelet-transformed system; returns (u, iterations).  The
         right-hand side goes to the device once and the solution comes back once: in
         between, every vector of the iteration is device-resident (the callback sees
         device vectors; source.linop.host_vector copies one out).  on_host=True runs
         the reference's wiring literally -- flat NumPy vectors, one round trip over
-        PCIe per operator apply."""
+        PCIe per operator apply.  `rhs`: another right-hand side on the trial space in
+        place of f -- a flat NumPy vector or a device vector (what
+        ``sample_along_adjoint`` returned: S^-1 E^T r is the gradient of a point-data
+        misfit)."""
+        from source.linop import _is_device_vector
+        f = self.f if rhs is None else rhs
+        if _is_device_vector(f):
+            assert f.N == self.N and f.M == self.M, 'rhs= takes a vector of the trial space'
+        else:
+            assert np.size(f) == self.N * self.M, 'rhs= takes a vector of the trial space'
         if on_host:
-            w, iters = PCG(self.WT_S_W, self.P, self.WT @ self.f, callback=callback)
+            f = host_vector(f) if _is_device_vector(f) else f
+            w, iters = PCG(self.WT_S_W, self.P, self.WT @ f, callback=callback)
             return self.W @ w, iters
-        rhs = device_vector(self.f, self.N)
-        w, iters = PCG(self.WT_S_W, self.P, self.WT @ rhs, callback=callback)
+        f = f if _is_device_vector(f) else device_vector(f, self.N)
+        w, iters = PCG(self.WT_S_W, self.P, self.WT @ f, callback=callback)
         return host_vector(self.W @ w), iters
 
     def errors(self, u):
@@ -176,6 +186,30 @@ class HeatEquation:
         from source.sampling import sample_pairs_collective
         u = self._trial_vector(u)
         return sample_pairs_collective(self.sample_plan, u, times, points, fields)
+
+    def sample_along_adjoint(self, weights, times, points, field='u', out=None, accumulate=False):
+        """The adjoint E^T of ``sample_along``: numbers given at the pairs (times[p],
+        points[p]) as a functional on the trial space (`weights` (n_p,), for field='grad'
+        (d, n_p)).  Returns (vec, used) as heateq_mpi.py's sample_along_adjoint(): a DEVICE
+        vector (source.linop.host_vector copies it out; ``solve(rhs=vec)`` takes it as it is)
+        and a device bool tensor (n_p,), False where a pair is outside the mesh or [0, T] and
+        contributes nothing.  `out`: a flat NumPy vector or a device vector to overwrite or,
+        with accumulate=True, to add to (a NumPy vector is copied to the device, not changed).
+        One rank, so nothing here is collective."""
+        from source.linop import _is_device_vector, self_distribution
+        from source.sampling import FIELDS, SamplePlan
+        if field not in FIELDS:  # before a plan is built for it
+            raise ValueError('field must be one of %s, not %r' % (FIELDS, field))
+        if out is not None and not _is_device_vector(out):
+            if np.size(out) != self.N * self.M:
+                raise ValueError('out is no vector of the trial space')
+            out = device_vector(out, self.N)
+        if self.sample_plan is None:
+            mesh_space, mesh_time = self._sample_meshes
+            self.sample_plan = SamplePlan(mesh_space, mesh_time)
+        plan = self.sample_plan
+        return plan.adjoint_pairs(self_distribution(self.N, self.M), weights, times, plan.locate(points), field=field,
+                                  out=out, accumulate=accumulate)
 
     def error_norms(self, u, exact=None, exact_grad=None, times=None):
         """|| u - u_h || of a trial-space vector `u` -- flat NumPy vector or device vector

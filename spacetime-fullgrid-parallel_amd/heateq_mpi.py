@@ -507,14 +507,20 @@ class HeatEquationMPI:
         out = self.Kinv_x.apply(y.buf, n_loc=y.n_loc)
         return KronVectorMPI.around(self.dofs_test, element_block_mix(self.dofs_test, self._minv_blocks, out))
 
-    def solve(self, callback=None, history=None, eps=1e-6, kmax=100000):
+    def solve(self, callback=None, history=None, eps=1e-6, kmax=100000, rhs=None):
         """PCG on the wavelet-transformed system with the forcing's right-hand side
         (reference heateq.py:146-150); returns (u = W w, iterations).  `eps`, `kmax`: PCG's
         stopping rule (r.Pr < eps^2; the reference's 1e-6 by default) -- an algebraic error of
         1e-6 in the energy norm shows in the fifth digit of || u - u_h || (error_norms), a
-        smaller eps removes it."""
-        assert self.f is not None, 'solve() is the path of a problem with forcing; without: PCG on rhs'
-        w, iters = PCG(self.WT_S_W, self.P, self.WT @ self.f, eps=eps, kmax=kmax, callback=callback, history=history)
+        smaller eps removes it.  `rhs`: another right-hand side on the trial space (a
+        KronVectorMPI, e.g. what ``sample_along_adjoint`` returned: S is symmetric, so
+        S^-1 E^T r is the gradient of a point-data misfit) in place of the forcing's f; with
+        it a problem without forcing can call solve() too."""
+        f = self.f if rhs is None else rhs
+        assert f is not None, 'solve() is the path of a problem with forcing; without: PCG on rhs'
+        if rhs is not None:
+            assert rhs.dofs_distr.N == self.N and rhs.M == self.M, 'rhs= takes a vector of the trial space'
+        w, iters = PCG(self.WT_S_W, self.P, self.WT @ f, eps=eps, kmax=kmax, callback=callback, history=history)
         return self.W @ w, iters
 
     def errors(self, u):
@@ -562,6 +568,31 @@ class HeatEquationMPI:
         ``sample``; the plan is built by the first call of either."""
         from source.sampling import sample_pairs_collective
         return sample_pairs_collective(self._sample_plan_for(u), u, times, points, fields)
+
+    def sample_along_adjoint(self, weights, times, points, field='u', out=None, accumulate=False):
+        """The adjoint E^T of ``sample_along``: numbers given at the PAIRS (times[p], points[p])
+        as a functional on the trial space -- v -> sum_p weights[p] v_h(t_p, x_p) for
+        field='u', the same with d/dt v_h for 'dt', sum_p weights[:, p] . grad v_h(t_p, x_p)
+        for 'grad' (`weights` (n_p,), for 'grad' (d, n_p); NumPy arrays or device tensors;
+        `points` also what ``sample_plan.locate`` returned).  Returns (vec, used): a
+        KronVectorMPI of the trial space -- `out` if given, overwritten, or added to with
+        accumulate=True -- and a device bool tensor (n_p,), False where the point is outside
+        the mesh or the time is NaN or outside [0, T] (checked on the device): such a pair
+        contributes nothing.  With r = sample_along(u) - data, ``solve(rhs=vec)`` is the
+        gradient of the misfit 1/2 |r|^2 with respect to the right-hand side.  Every rank
+        passes ALL pairs and builds the columns it owns: no communication, and -- every entry
+        being a sum of one fixed order, not an atomic scatter -- independent of the number of
+        ranks, bit for bit, as ``sample_along``; the plan is built by the first call of any of
+        the sampling methods."""
+        from source.sampling import FIELDS, SamplePlan
+        if field not in FIELDS:  # before a plan is built for it
+            raise ValueError('field must be one of %s, not %r' % (FIELDS, field))
+        if self.sample_plan is None:
+            mesh_space, mesh_time = self._sample_meshes
+            self.sample_plan = SamplePlan(mesh_space, mesh_time)
+        plan = self.sample_plan
+        return plan.adjoint_pairs(self.dofs_distr, weights, times, plan.locate(points), field=field, out=out,
+                                  accumulate=accumulate)
 
     def error_norms(self, u, exact=None, exact_grad=None, times=None):
         """|| u - u_h || of a trial-space vector `u` (KronVectorMPI) against `exact`

@@ -269,6 +269,9 @@ _PROTOTYPES = {
     'stk_sample_pairs': (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_p, c_f64, c_i32, c_i32, c_i32, c_i32, c_i32, c_p,
                                         c_i32, c_i64, c_p]),
     'stk_sample_grad_coeffs': (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p]),
+    'stk_sample_pairs_adjoint_work_size': (ctypes.c_int, [c_i64, c_i32, c_p]),
+    'stk_sample_pairs_adjoint': (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_p, c_f64, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                                c_p, c_p, c_i64, c_i32, c_i32, c_p, c_p, c_i64]),
     'stk_err_plan_create': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_i64, c_p, ctypes.POINTER(c_p)]),
     'stk_err_plan_destroy': (ctypes.c_int, [c_p]),
     'stk_err_points': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p]),

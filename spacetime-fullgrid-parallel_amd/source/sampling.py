@@ -17,6 +17,10 @@ rasters of time slices, probes at points, cuts along lines.
   trajectory, a set of tracers -- without the block they are the diagonal of, and with
   the derivatives: u_h, d/dt u_h and grad u_h per point (stk_sample_pairs).  The block
   forms of the derivatives are ``evaluate(..., field='dt' | 'grad')``.
+* ``adjoint_pairs(distr, weights, times, located, field)``: the adjoint E^T of the pairs --
+  numbers given at (t_p, x_p) as a functional on the trial space, the right-hand side of
+  a solve that uses point data (stk_sample_pairs_adjoint): store, stable sort, sum; no
+  float atomics, the same doubles whatever the launch and the number of ranks.
 
 Scope: vectors of the TRIAL space (continuous piecewise linear in time).  Test-space
 vectors (discontinuous in time) and second derivatives are not served.
@@ -249,6 +253,56 @@ class SamplePlan:
         on the device: nothing here waits for it).  The sum over the ranks is the value."""
         return self._split_rows(*self._pair_rows(vec, times, located, fields))
 
+    def adjoint_pairs(self, distr, weights, times, located, field='u', out=None, accumulate=False):
+        """E^T of ``evaluate_pairs``: the numbers `weights` given at the PAIRS (times[p],
+        point p) as a functional on the trial space, v -> sum_p weights[p] v_h(t_p, x_p)
+        (field='u'), ... d/dt v_h (field='dt') or sum_p weights[:, p] . grad v_h (field='grad'),
+        on the columns the distribution `distr` (a DofDistributionMPI) gives this rank
+        (stk_sample_pairs_adjoint).  `weights`: (n_p,), for 'grad' (d, n_p); `times`: (n_p,);
+        NumPy arrays or device tensors.  Returns (vec, used): the KronVectorMPI -- `out` if
+        given, overwritten, or added to with accumulate=True -- and a device bool tensor
+        (n_p,), False where the point is outside the mesh or the time is NaN or outside
+        [0, T]: such a pair contributes nothing (decided on the device: nothing here waits).
+        No float atomics: every entry is a sum of one fixed shape, the same whatever the launch
+        and whatever the number of ranks -- every rank passes ALL pairs and gets its own
+        columns, with no communication.  Wrong shapes or field names raise ValueError before
+        anything touches the GPU.  The workspace is kept by the plan and grows with n_p."""
+        weights, times = _check_adjoint_arguments(self.d, located.n_p, weights, times, field)
+        if distr.M != self.n_free or distr.N < 2:
+            raise ValueError('a distribution of %d x %d dofs on a plan of %d free dofs' % (distr.N, distr.M, self.n_free))
+        if out is None and accumulate:
+            raise ValueError('accumulate=True needs the vector to add to: out=')
+        if out is not None and (out.dofs_distr.N, out.M, out.t_begin, out.t_end) != (distr.N, distr.M, distr.t_begin,
+                                                                                    distr.t_end):
+            raise ValueError('out is no vector of this distribution')
+        import torch
+
+        from .mpi_vector import KronVectorMPI
+        _lib = self._lib
+        mesh_time = self._time_mesh_of(distr)
+        if out is None:
+            out = KronVectorMPI(distr)
+        else:
+            out._invalidate()
+        dev, n_p = out.buf.device, located.n_p
+        as_dev = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.array(a, dtype=np.float64, order='C'))).to(
+            device=dev, dtype=torch.float64).contiguous()
+        weights, times = as_dev(weights), as_dev(times)
+        used = torch.empty(n_p, dtype=torch.uint8, device=dev)
+        size = ctypes.c_int64()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().stk_sample_pairs_adjoint_work_size(n_p, self.d, ctypes.addressof(size)))
+            work = getattr(self, '_adjoint_work', None)
+            if work is None or work.numel() < size.value or work.device != dev:
+                self._adjoint_work = work = None  # the old one goes first
+                self._adjoint_work = work = torch.empty(max(size.value, 256), dtype=torch.uint8, device=dev)
+            assert _lib.ptr(work) % 256 == 0
+            _lib.check(_lib.lib().stk_sample_pairs_adjoint(
+                _lib.stream(), self._plan, n_p, _lib.ptr(located.cell), _lib.ptr(located.lam), _lib.ptr(times),
+                float(mesh_time.h), distr.N, distr.t_begin, distr.M, out.n_loc, out.ld, _lib.ptr(out.buf), _lib.ptr(weights),
+                n_p, 1 << FIELDS.index(field), int(bool(accumulate)), _lib.ptr(used), _lib.ptr(work), work.numel()))
+        return out, used.bool()
+
 
 FIELDS = ('u', 'dt', 'grad')
 
@@ -260,6 +314,22 @@ def field_mask(fields):
     if not names or any(f not in FIELDS for f in names):
         raise ValueError('fields must name some of %s, not %r' % (FIELDS, fields))
     return sum(1 << FIELDS.index(f) for f in set(names))
+
+
+def _check_adjoint_arguments(d, n_p, weights, times, field):
+    """(weights, times) of ``SamplePlan.adjoint_pairs`` -- device tensors as they came,
+    anything else as float64 NumPy arrays -- or ValueError: `field` one name of FIELDS,
+    weights (n_p,), for 'grad' (d, n_p), times (n_p,).  Touches no GPU."""
+    if not isinstance(field, str) or field not in FIELDS:
+        raise ValueError('field must be one of %s, not %r' % (FIELDS, field))
+    host = lambda a: a if hasattr(a, 'is_cuda') else np.asarray(a, dtype=np.float64)
+    weights, times = host(weights), host(times)
+    want = (d, n_p) if field == 'grad' else (n_p,)
+    if tuple(weights.shape) != want:
+        raise ValueError("weights of shape %s; field '%s' at %d points takes %s" % (tuple(weights.shape), field, n_p, want))
+    if tuple(times.shape) != (n_p,):
+        raise ValueError('times of shape %s for %d points' % (tuple(times.shape), n_p))
+    return weights, times
 
 
 def sample_collective(plan, vec, times, points, field='u'):
