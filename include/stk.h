@@ -804,7 +804,12 @@ int stk_kron_pack_elem_apply_t(void *stream, const stk_pack_pattern *pattern_hos
  * y = (W_t kron I) x or (W_t^T kron I) x in the interleaved numbering, all
  * J levels in one pass (WaveletTransformOp._matmat / _rmatmat,
  * wavelets.py:106-134; same operator as the composite of
- * wavelets.py:172-198 on one rank).  Requires n_loc == 2^J + 1. */
+ * wavelets.py:172-198 on one rank).  Requires n_loc == 2^J + 1, 0 <= J <= 11,
+ * ld >= n_loc; x == y is allowed.  Padding (columns n_loc .. ld - 1): padding of y
+ * is zero provided padding of x is zero; the data columns never read it.  (With
+ * 1 <= J <= 7, ld == n_loc + 1 and both pointers 16-byte aligned, whole rows move
+ * as they are and y's padding column is x's; in every other case y's padding is
+ * written as zero whatever x holds there.) */
 int stk_wavelet_apply(void *stream, int32_t M, int32_t J, int32_t ld,
                       int32_t transposed, const double *x, double *y);
 

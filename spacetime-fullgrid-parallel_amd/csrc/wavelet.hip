@@ -102,7 +102,7 @@ __global__ __launch_bounds__(WBS) void wavelet_kernel(int32_t M, int32_t J, int3
 }
 
 // ---------------------------------------------------------------------------
-// Register variant for J <= 6 and ld == 2^J + 2: one wavefront per workgroup
+// Register variant for 1 <= J <= 7 and ld == 2^J + 2: one wavefront per workgroup
 // owns 64 consecutive time columns, which are one contiguous run of memory.
 // The run is copied to LDS with 16-byte loads, every lane then pulls its own
 // column into registers, runs all J levels there (compile-time unrolled, the
@@ -234,7 +234,8 @@ extern "C" int stk_wavelet_apply(void *stream, int32_t M, int32_t J, int32_t ld,
     STK_REQUIRE(M > 0 && J >= 0 && J <= 11, "stk_wavelet_apply: bad M=%d J=%d", M, J);
     const int N = (1 << J) + 1;
     STK_REQUIRE(ld >= N, "stk_wavelet_apply: ld=%d < 2^J+1=%d", ld, N);
-    STK_REQUIRE(x && y, "stk_wavelet_apply: null pointer");
+    STK_REQUIRE(x, "stk_wavelet_apply: x is a null pointer");
+    STK_REQUIRE(y, "stk_wavelet_apply: y is a null pointer");
     STK_REQUIRE(N <= TILE_ELEMS, "stk_wavelet_apply: J too large");
     if (J >= 1 && J <= 7 && ld == N + 1 &&
         (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {

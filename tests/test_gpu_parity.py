@@ -206,7 +206,9 @@ def test_wavelets_match_reference_golden(stk, g3):
     assert np.array_equal(W.levels, g3['levels'])
     assert relerr(_np(W @ x), g3['W']) < TOL
     assert relerr(_np(WT @ x), g3['WT']) < TOL
-    # the per-level composite (what runs across ranks) gives the same
+    # without the one-rank call the operators take the all-to-all form (mode 'transpose', what
+    # runs across ranks) and give the same; the per-level composite (mode 'composite') is
+    # held to its own bound in test_wavelet_kernels_gpu.py
     W._fused = WT._fused = None
     assert relerr(_np(W @ x), g3['W']) < TOL
     assert relerr(_np(WT @ x), g3['WT']) < TOL
@@ -224,8 +226,8 @@ def test_wavelet_op_matrices(stk):
             assert np.allclose(as_matrix(op.T), g['WT_' + key], rtol=0,
                                atol=1e-14)
             assert np.array_equal(np.asarray(op.levels), g['levels_' + key])
-    # J = 6, 7: register kernel (full 64-column tiles and a ragged last one);
-    # J = 8: the generic LDS kernel
+    # all of this test runs the generic LDS kernel: WaveletTransformOp passes ld = N, and the
+    # register kernel wants ld = N + 1 (its own tests: test_wavelet_kernels_gpu.py)
     from oracle import wavelets as ow
     for J in (6, 7, 8):
         op = WaveletTransformOp(J, interleaved=True)
