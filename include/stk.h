@@ -1062,7 +1062,8 @@ int stk_p1_load_sum_2d(int64_t nv, int64_t nt, const double *points,
  * in which the gather pass visits them (stk_tile_order's; a performance hint, results
  * never depend on it; null = ascending).  It uploads them, computes |T| per cell by
  * the expression of stk_p1_load_sum_2d (tetrahedra: the cofactor expansion of
- * source/assembly.py) and builds for every free dof the list of its (cell, local
+ * source/assembly.py; csrc/p1_mesh.h holds the one definition that the load vectors, the
+ * error norms and the sampler use) and builds for every free dof the list of its (cell, local
  * vertex) incidences in ascending order.  max_k = the most time points one
  * stk_load_columns call takes (1..STK_LOAD_MAX_K): the plan owns max_k * (d + 1) * nc
  * doubles of workspace, so one plan serves one stream at a time.
@@ -1268,9 +1269,9 @@ int stk_sample_pairs_adjoint(void *stream, const stk_sample_plan *plan, int64_t 
  * stk_sample_plan_create take, with their checks: points [nv][d], cells [nc][d + 1]
  * (d = 2 or 3), free_vertices [n_free] = the vertex of every slab row.  Nothing assumes
  * that the cells cover anything.  It uploads the cells (int32) and the map vertex -> slab
- * row (-1 for a boundary vertex, whose value is 0), and computes per cell |T| by the
- * expressions of stk_load_plan_create and the gradients of the barycentric coordinates
- * [nc][d + 1][d]: with e_r = p_r - p_0,
+ * row (-1 for a boundary vertex, whose value is 0), and computes per cell |T| and the
+ * gradients of the barycentric coordinates [nc][d + 1][d] by the simplex routine of
+ * csrc/p1_mesh.h that stk_load_plan_create and the sampler call: with e_r = p_r - p_0,
  *     triangles   det = e1[0] e2[1] - e1[1] e2[0],
  *                 grad l_1 = (e2[1] / det, -e2[0] / det),  grad l_2 = (-e1[1] / det, e1[0] / det);
  *     tetrahedra  det = (e1[0] C_00 + e1[1] C_10) + e1[2] C_20 with the cofactors
@@ -1283,8 +1284,8 @@ int stk_sample_pairs_adjoint(void *stream, const stk_sample_plan *plan, int64_t 
  *
  * The rule is the caller's, per call, as for the load vectors: HOST arrays rule_points
  * [nq][d + 1] (barycentric) and rule_weights [nq], 1 <= nq <= STK_ERR_MAX_NQ.
- * stk_err_points writes the DEVICE array q_points [d][nc][nq] by the expression of
- * stk_load_points -- the same doubles.
+ * stk_err_points writes the DEVICE array q_points [d][nc][nq] with the kernel of
+ * stk_load_points (csrc/p1_mesh.h) -- the same doubles.
  *
  * stk_err_element takes, for the n_k (1..STK_ERR_MAX_K) time points of one time element,
  * HOST arrays w_lo, w_hi, c [n_k] and DEVICE arrays f [n_k][nc][nq] (the exact solution at

@@ -5,8 +5,8 @@
 //
 //  * stk_err_plan_create  uploads the mesh and the vertex -> slab-row map, computes |T| and
 //                         the gradients of the barycentric coordinates per cell
-//  * stk_err_points       the quadrature points of every cell, [d][nc][nq]: the expression
-//                         of stk_load_points
+//  * stk_err_points       the quadrature points of every cell, [d][nc][nq]: the kernel of
+//                         stk_load_points (p1_mesh.h)
 //  * stk_err_element      f [n_k][nc][nq] (and gf [n_k][d][nc][nq]) at those points for the
 //                         n_k time points of ONE time element + the two rows of nodal values
 //                         at its ends -> four sums over the mesh
@@ -21,42 +21,32 @@
 // cells [256 i, 256 i + 256) whatever the grid, so every sum has one shape, fixed by nc.
 //
 // ARITHMETIC: every product and every sum rounded on its own -- contraction is SWITCHED OFF
-// for this file (the pragma below and -ffp-contract=off in the Makefile), as for the load
-// engine and the sampler, and no kernel here calls fma.
-#include <cmath>
-#include <vector>
-
-#include "stk_common.h"
+// for this file and for p1_mesh.h (their pragmas and -ffp-contract=off in the Makefile), as
+// for the load engine and the sampler, and no kernel here calls fma.
+#include "p1_mesh.h"
 
 #pragma clang fp contract(off)
 
 struct stk_err_plan {
     int32_t d;
     int64_t nv, nc, n_free, n_tiles;
-    double *points;   // [nv][d]
-    int32_t *cells;   // [nc][d + 1]
-    int32_t *row_of;  // [nv]: slab row of a vertex, -1 on the boundary
-    double *vol;      // [nc]
-    double *grad;     // [nc][d + 1][d]
-    double *work;     // [n_tiles][4] partials of a call in flight
+    p1_mesh_dev mesh;
+    double *vol;   // [nc]
+    double *grad;  // [nc][d + 1][d]
+    double *work;  // [n_tiles][4] partials of a call in flight
 };
 
 namespace {
 
 constexpr int BS = 256;
 
-struct err_rule {
-    double w[STK_ERR_MAX_NQ];
-    double l[STK_ERR_MAX_NQ * 4];  // l[q (d + 1) + a]
-};
-
 struct err_times {
     double w_lo[STK_ERR_MAX_K], w_hi[STK_ERR_MAX_K], c[STK_ERR_MAX_K];
 };
 
-// |T| by the expressions of load_volume_kernel (load_dev.hip); grad lambda_a from the same
-// cofactors over the same determinant (source/assembly.py:_simplex_geometry): each
-// quotient rounded once, grad lambda_0 = -((g_1 + g_2) [+ g_3])
+// |T| and grad lambda_a per cell (p1_volume, p1_gradients), but grad lambda_0 =
+// -((g_1 + g_2) [+ g_3]), the expression of source/assembly.py:_simplex_geometry: it gives
+// -0.0 where p1_gradients gives +0.0 (g_1 = -g_2), the only doubles in which the two differ
 template <int D>
 __global__ __launch_bounds__(BS) void err_geometry_kernel(int64_t nc, const double *__restrict__ p,
                                                           const int32_t *__restrict__ cells, double *__restrict__ vol,
@@ -64,75 +54,20 @@ __global__ __launch_bounds__(BS) void err_geometry_kernel(int64_t nc, const doub
 {
     const int64_t stride = (int64_t)gridDim.x * BS;
     for (int64_t t = (int64_t)blockIdx.x * BS + threadIdx.x; t < nc; t += stride) {
-        const int32_t *c = cells + (D + 1) * t;
-        const double *p0 = p + D * (int64_t)c[0];
-        double e[D][D];
-#pragma unroll
-        for (int r = 0; r < D; ++r)
-#pragma unroll
-            for (int k = 0; k < D; ++k) e[r][k] = p[D * (int64_t)c[r + 1] + k] - p0[k];
+        const p1_simplex<D> s = p1_simplex_of<D>(p, cells + (D + 1) * t);
+        vol[t] = p1_volume(s);
         double g[D + 1][D];  // g[a][j]
-        if constexpr (D == 2) {
-            const double det = e[0][0] * e[1][1] - e[0][1] * e[1][0];
-            vol[t] = fabs(det) / 2.0;
-            g[1][0] = e[1][1] / det, g[1][1] = (-e[1][0]) / det;
-            g[2][0] = (-e[0][1]) / det, g[2][1] = e[0][0] / det;
-        } else {
-            double adj[3][3];  // adj[j][a]: E^{-1} = adj / det, column a = grad lambda_{a + 1}
-            adj[0][0] = e[1][1] * e[2][2] - e[1][2] * e[2][1];
-            adj[1][0] = e[1][2] * e[2][0] - e[1][0] * e[2][2];
-            adj[2][0] = e[1][0] * e[2][1] - e[1][1] * e[2][0];
-            adj[0][1] = e[0][2] * e[2][1] - e[0][1] * e[2][2];
-            adj[1][1] = e[0][0] * e[2][2] - e[0][2] * e[2][0];
-            adj[2][1] = e[0][1] * e[2][0] - e[0][0] * e[2][1];
-            adj[0][2] = e[0][1] * e[1][2] - e[0][2] * e[1][1];
-            adj[1][2] = e[0][2] * e[1][0] - e[0][0] * e[1][2];
-            adj[2][2] = e[0][0] * e[1][1] - e[0][1] * e[1][0];
-            const double det = e[0][0] * adj[0][0] + e[0][1] * adj[1][0] + e[0][2] * adj[2][0];
-            vol[t] = fabs(det) / 6.0;
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) g[a + 1][j] = adj[j][a] / det;
-        }
+        p1_gradients(s, g);
 #pragma unroll
         for (int j = 0; j < D; ++j) {
-            double s = g[1][j] + g[2][j];
-            if constexpr (D == 3) s = s + g[3][j];
-            g[0][j] = -s;
+            double sum = g[1][j] + g[2][j];
+            if constexpr (D == 3) sum = sum + g[3][j];
+            g[0][j] = -sum;
         }
 #pragma unroll
         for (int a = 0; a <= D; ++a)
 #pragma unroll
             for (int j = 0; j < D; ++j) grad[((D + 1) * t + a) * D + j] = g[a][j];
-    }
-}
-
-// one lane per (cell, q): l0 p0 + l1 p1 + ..., summed from the left -- load_points_kernel
-template <int D>
-__global__ __launch_bounds__(BS) void err_points_kernel(int64_t total, int32_t nq, const double *__restrict__ p,
-                                                        const int32_t *__restrict__ cells, err_rule r,
-                                                        double *__restrict__ out)
-{
-    __shared__ double rule[STK_ERR_MAX_NQ * (D + 1)];
-    if (threadIdx.x == 0)
-        for (int j = 0; j < nq * (D + 1); ++j) rule[j] = r.l[j];
-    __syncthreads();
-    const int64_t stride = (int64_t)gridDim.x * BS;
-    for (int64_t idx = (int64_t)blockIdx.x * BS + threadIdx.x; idx < total; idx += stride) {
-        const int64_t t = idx / nq;
-        const int q = (int)(idx - t * nq);
-        const int32_t *c = cells + (D + 1) * t;
-        double l[D + 1];
-#pragma unroll
-        for (int a = 0; a <= D; ++a) l[a] = rule[q * (D + 1) + a];
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            double x = l[0] * p[D * (int64_t)c[0] + k];
-#pragma unroll
-            for (int a = 1; a <= D; ++a) x = x + l[a] * p[D * (int64_t)c[a] + k];
-            out[k * total + idx] = x;
-        }
     }
 }
 
@@ -155,7 +90,7 @@ template <int D, bool GRAD>
 __global__ __launch_bounds__(BS) void err_cells_kernel(int64_t nc, int64_t n_tiles, int32_t nq, int32_t n_k,
                                                        const int32_t *__restrict__ cells,
                                                        const int32_t *__restrict__ row_of, const double *__restrict__ vol,
-                                                       const double *__restrict__ grad, err_rule r, err_times tm,
+                                                       const double *__restrict__ grad, p1_rule r, err_times tm,
                                                        const double *__restrict__ f, const double *__restrict__ gf,
                                                        const double *__restrict__ u_lo, int64_t stride_lo,
                                                        const double *__restrict__ u_hi, int64_t stride_hi,
@@ -277,29 +212,11 @@ __global__ __launch_bounds__(BS) void err_finish_kernel(int64_t n_tiles, int64_t
 void release(stk_err_plan *p)
 {
     if (!p) return;
-    void *arrays[] = {p->points, p->cells, p->row_of, p->vol, p->grad, p->work};
+    p1_mesh_free(&p->mesh);
+    void *arrays[] = {p->vol, p->grad, p->work};
     for (void *a : arrays)
         if (a) (void)hipFree(a);
     delete p;
-}
-
-template <typename T>
-int upload(T **dst, const T *src, size_t n)
-{
-    STK_HIP(hipMalloc((void **)dst, (n ? n : 1) * sizeof(T)));
-    if (n) STK_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
-int fill_rule(const char *who, const stk_err_plan *p, int32_t nq, const double *w, const double *l, err_rule *r)
-{
-    STK_REQUIRE(nq >= 1 && nq <= STK_ERR_MAX_NQ, "%s: %d quadrature points (1..%d)", who, nq, STK_ERR_MAX_NQ);
-    STK_REQUIRE(l, "%s: no rule points", who);
-    for (int q = 0; q < nq; ++q) {
-        r->w[q] = w ? w[q] : 0.0;
-        for (int a = 0; a <= p->d; ++a) r->l[q * (p->d + 1) + a] = l[q * (p->d + 1) + a];
-    }
-    return 0;
 }
 
 }  // namespace
@@ -309,29 +226,15 @@ extern "C" int stk_err_plan_create(int32_t d, int64_t nv, int64_t nc, const doub
 {
     STK_REQUIRE((d == 2 || d == 3) && nv > 0 && nc > 0 && points && cells && n_free > 0 && free_vertices && out,
                 "stk_err_plan_create: bad arguments");
+    STK_REQUIRE(n_free < ((int64_t)1 << 31), "stk_err_plan_create: mesh too large for 32-bit tables");
+    if (int rc = p1_check_mesh("stk_err_plan_create", d, nv, nc, points, cells)) return rc;
+    std::vector<int32_t> row_of;
+    if (int rc = p1_row_of("stk_err_plan_create", nv, n_free, free_vertices, &row_of)) return rc;
     const int64_t ns = (int64_t)(d + 1) * nc;
-    STK_REQUIRE(nv < ((int64_t)1 << 31) && ns < ((int64_t)1 << 31) && n_free < ((int64_t)1 << 31),
-                "stk_err_plan_create: mesh too large for 32-bit tables");
-    for (int64_t q = 0; q < ns; ++q)
-        STK_REQUIRE(cells[q] >= 0 && cells[q] < nv, "stk_err_plan_create: cell %lld names vertex %lld",
-                    (long long)(q / (d + 1)), (long long)cells[q]);
-    std::vector<int32_t> row_of((size_t)nv, -1);
-    for (int64_t i = 0; i < n_free; ++i) {
-        const int64_t v = free_vertices[i];
-        STK_REQUIRE(v >= 0 && v < nv && row_of[(size_t)v] < 0,
-                    "stk_err_plan_create: free dof %lld is vertex %lld (out of range or named twice)", (long long)i,
-                    (long long)v);
-        row_of[(size_t)v] = (int32_t)i;
-    }
-    std::vector<int32_t> cells32((size_t)ns);
-    for (int64_t q = 0; q < ns; ++q) cells32[q] = (int32_t)cells[q];
 
     stk_err_plan *p = new stk_err_plan();
     p->d = d, p->nv = nv, p->nc = nc, p->n_free = n_free, p->n_tiles = (nc + BS - 1) / BS;
-    int rc = upload(&p->points, points, (size_t)nv * d);
-    if (!rc) rc = upload(&p->cells, cells32.data(), cells32.size());
-    if (!rc) rc = upload(&p->row_of, row_of.data(), row_of.size());
-    if (rc) {
+    if (int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, cells, &row_of)) {
         release(p);
         return rc;
     }
@@ -341,9 +244,9 @@ extern "C" int stk_err_plan_create(int32_t d, int64_t nv, int64_t nc, const doub
     if (e == hipSuccess) {
         const dim3 grid(stk_flat_grid(nc, BS));
         if (d == 2)
-            hipLaunchKernelGGL(err_geometry_kernel<2>, grid, dim3(BS), 0, 0, nc, p->points, p->cells, p->vol, p->grad);
+            hipLaunchKernelGGL(err_geometry_kernel<2>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol, p->grad);
         else
-            hipLaunchKernelGGL(err_geometry_kernel<3>, grid, dim3(BS), 0, 0, nc, p->points, p->cells, p->vol, p->grad);
+            hipLaunchKernelGGL(err_geometry_kernel<3>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol, p->grad);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -367,17 +270,7 @@ extern "C" int stk_err_points(void *stream, const stk_err_plan *plan, int32_t nq
 {
     const stk_timed timed_(STK_OP_SPACE, stream);
     STK_REQUIRE(plan && q_points, "stk_err_points: null pointer");
-    err_rule r = {};
-    if (int rc = fill_rule("stk_err_points", plan, nq, nullptr, rule_points, &r)) return rc;
-    const int64_t total = plan->nc * nq;
-    const dim3 grid(stk_flat_grid(total, BS));
-    hipStream_t st = stk_stream(stream);
-    if (plan->d == 2)
-        hipLaunchKernelGGL(err_points_kernel<2>, grid, dim3(BS), 0, st, total, nq, plan->points, plan->cells, r, q_points);
-    else
-        hipLaunchKernelGGL(err_points_kernel<3>, grid, dim3(BS), 0, st, total, nq, plan->points, plan->cells, r, q_points);
-    STK_LAUNCH_CHECK();
-    return 0;
+    return p1_points("stk_err_points", stream, plan, nq, rule_points, q_points);
 }
 
 extern "C" int stk_err_element(void *stream, stk_err_plan *plan, int32_t nq, const double *rule_weights,
@@ -391,8 +284,8 @@ extern "C" int stk_err_element(void *stream, stk_err_plan *plan, int32_t nq, con
     STK_REQUIRE(n_k >= 1 && n_k <= STK_ERR_MAX_K, "stk_err_element: %d time points (1..%d)", n_k, STK_ERR_MAX_K);
     STK_REQUIRE(stride_lo >= 1 && stride_hi >= 1, "stk_err_element: row strides %lld and %lld (at least 1)",
                 (long long)stride_lo, (long long)stride_hi);
-    err_rule r = {};
-    if (int rc = fill_rule("stk_err_element", plan, nq, rule_weights, rule_points, &r)) return rc;
+    p1_rule r = {};
+    if (int rc = p1_fill_rule("stk_err_element", plan->d, nq, rule_weights, rule_points, &r)) return rc;
     err_times tm = {};
     for (int k = 0; k < n_k; ++k) tm.w_lo[k] = w_lo[k], tm.w_hi[k] = w_hi[k], tm.c[k] = c[k];
     hipStream_t st = stk_stream(stream);
@@ -400,8 +293,8 @@ extern "C" int stk_err_element(void *stream, stk_err_plan *plan, int32_t nq, con
     const int64_t n_tiles = plan->n_tiles;
     const dim3 grid((unsigned)(n_tiles < 256 * 16 ? n_tiles : 256 * 16));
 #define STK_ERR_LAUNCH(D, GRAD)                                                                                          \
-    hipLaunchKernelGGL((err_cells_kernel<D, GRAD>), grid, dim3(BS), lds, st, plan->nc, n_tiles, nq, n_k, plan->cells,     \
-                       plan->row_of, plan->vol, plan->grad, r, tm, f, gf, u_lo, stride_lo, u_hi, stride_hi, plan->work)
+    hipLaunchKernelGGL((err_cells_kernel<D, GRAD>), grid, dim3(BS), lds, st, plan->nc, n_tiles, nq, n_k, plan->mesh.cells, \
+                       plan->mesh.row_of, plan->vol, plan->grad, r, tm, f, gf, u_lo, stride_lo, u_hi, stride_hi, plan->work)
     if (plan->d == 2) {
         if (gf)
             STK_ERR_LAUNCH(2, true);

@@ -22,20 +22,16 @@
 //
 // ARITHMETIC: the doubles of the host routines, bit for bit -- every product and every
 // sum is rounded on its own.  hipcc contracts a * b + c into a fused multiply-add in
-// device code by default; contraction is SWITCHED OFF for this file (the pragma below and
-// -ffp-contract=off in the Makefile), and no kernel here calls fma.
-#include <cmath>
-#include <vector>
-
-#include "stk_common.h"
+// device code by default; contraction is SWITCHED OFF for this file and for p1_mesh.h (their
+// pragmas and -ffp-contract=off in the Makefile), and no kernel here calls fma.
+#include "p1_mesh.h"
 
 #pragma clang fp contract(off)
 
 struct stk_load_plan {
     int32_t d, max_k;
     int64_t nv, nc, n_free, ns;  // ns = (d + 1) nc slots (cell, local vertex)
-    double *points;              // [nv][d]
-    int32_t *cells;              // [nc][d + 1]
+    p1_mesh_dev mesh;            // no row_of: the incidence lists below take its place
     double *vol;                 // [nc]
     int32_t *inc_ptr;            // [n_free + 1]
     int32_t *inc_slot;           // slots of free dof i: inc_ptr[i] .. inc_ptr[i + 1], ascending
@@ -47,78 +43,25 @@ namespace {
 
 constexpr int BS = 256;
 
-struct load_rule {
-    double w[STK_LOAD_MAX_NQ];
-    double l[STK_LOAD_MAX_NQ * 4];  // l[q (d + 1) + a]
-};
-
 struct load_coef {
     double c[STK_LOAD_MAX_K * 2];
 };
 
-// |T| by the expressions of the host: stk_p1_load_sum_2d for triangles,
-// source/assembly.py:_simplex_geometry (cofactors of the first column, summed from the
-// left) for tetrahedra
+// |T| per cell (p1_volume)
 template <int D>
 __global__ __launch_bounds__(BS) void load_volume_kernel(int64_t nc, const double *__restrict__ p,
                                                          const int32_t *__restrict__ cells, double *__restrict__ vol)
 {
     const int64_t stride = (int64_t)gridDim.x * BS;
-    for (int64_t t = (int64_t)blockIdx.x * BS + threadIdx.x; t < nc; t += stride) {
-        const int32_t *c = cells + (D + 1) * t;
-        const double *p0 = p + D * (int64_t)c[0];
-        double e[D][D];
-#pragma unroll
-        for (int r = 0; r < D; ++r)
-#pragma unroll
-            for (int k = 0; k < D; ++k) e[r][k] = p[D * (int64_t)c[r + 1] + k] - p0[k];
-        if constexpr (D == 2) {
-            vol[t] = fabs(e[0][0] * e[1][1] - e[0][1] * e[1][0]) / 2.0;
-        } else {
-            const double a00 = e[1][1] * e[2][2] - e[1][2] * e[2][1];
-            const double a10 = e[1][2] * e[2][0] - e[1][0] * e[2][2];
-            const double a20 = e[1][0] * e[2][1] - e[1][1] * e[2][0];
-            const double det = e[0][0] * a00 + e[0][1] * a10 + e[0][2] * a20;
-            vol[t] = fabs(det) / 6.0;
-        }
-    }
-}
-
-// one lane per (cell, q): l0 p0 + l1 p1 + ..., summed from the left
-template <int D>
-__global__ __launch_bounds__(BS) void load_points_kernel(int64_t total, int32_t nq, const double *__restrict__ p,
-                                                         const int32_t *__restrict__ cells, load_rule r,
-                                                         double *__restrict__ out)
-{
-    // the rule through LDS: a lane's q is its own, and the kernel arguments are read
-    // with indices the whole wavefront shares
-    __shared__ double rule[STK_LOAD_MAX_NQ * (D + 1)];
-    if (threadIdx.x == 0)
-        for (int j = 0; j < nq * (D + 1); ++j) rule[j] = r.l[j];
-    __syncthreads();
-    const int64_t stride = (int64_t)gridDim.x * BS;
-    for (int64_t idx = (int64_t)blockIdx.x * BS + threadIdx.x; idx < total; idx += stride) {
-        const int64_t t = idx / nq;
-        const int q = (int)(idx - t * nq);
-        const int32_t *c = cells + (D + 1) * t;
-        double l[D + 1];
-#pragma unroll
-        for (int a = 0; a <= D; ++a) l[a] = rule[q * (D + 1) + a];
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            double x = l[0] * p[D * (int64_t)c[0] + k];
-#pragma unroll
-            for (int a = 1; a <= D; ++a) x = x + l[a] * p[D * (int64_t)c[a] + k];
-            out[k * total + idx] = x;
-        }
-    }
+    for (int64_t t = (int64_t)blockIdx.x * BS + threadIdx.x; t < nc; t += stride)
+        vol[t] = p1_volume(p1_simplex_of<D>(p, cells + (D + 1) * t));
 }
 
 // blockIdx.y = time point; a workgroup walks tiles of BS cells.  LDS: BS max(nq, D + 1)
 // doubles, the values of f on the way in and the shares on the way out.
 template <int D>
 __global__ __launch_bounds__(BS) void load_shares_kernel(int64_t nc, int32_t nq, const double *__restrict__ f,
-                                                         const double *__restrict__ vol, load_rule r,
+                                                         const double *__restrict__ vol, p1_rule r,
                                                          double *__restrict__ shares)
 {
     extern __shared__ double lds[];
@@ -189,29 +132,11 @@ __global__ __launch_bounds__(BS) void load_gather_kernel(int64_t n_free, int64_t
 void release(stk_load_plan *p)
 {
     if (!p) return;
-    void *arrays[] = {p->points, p->cells, p->vol, p->inc_ptr, p->inc_slot, p->order, p->shares};
+    p1_mesh_free(&p->mesh);
+    void *arrays[] = {p->vol, p->inc_ptr, p->inc_slot, p->order, p->shares};
     for (void *a : arrays)
         if (a) (void)hipFree(a);
     delete p;
-}
-
-template <typename T>
-int upload(T **dst, const std::vector<T> &src)
-{
-    STK_HIP(hipMalloc((void **)dst, (src.empty() ? 1 : src.size()) * sizeof(T)));
-    if (!src.empty()) STK_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
-int fill_rule(const char *who, const stk_load_plan *p, int32_t nq, const double *w, const double *l, load_rule *r)
-{
-    STK_REQUIRE(nq >= 1 && nq <= STK_LOAD_MAX_NQ, "%s: %d quadrature points (1..%d)", who, nq, STK_LOAD_MAX_NQ);
-    STK_REQUIRE(l, "%s: no rule points", who);
-    for (int q = 0; q < nq; ++q) {
-        r->w[q] = w ? w[q] : 0.0;
-        for (int a = 0; a <= p->d; ++a) r->l[q * (p->d + 1) + a] = l[q * (p->d + 1) + a];
-    }
-    return 0;
 }
 
 }  // namespace
@@ -224,11 +149,8 @@ extern "C" int stk_load_plan_create(int32_t d, int64_t nv, int64_t nc, const dou
                 "stk_load_plan_create: bad arguments");
     STK_REQUIRE(max_k >= 1 && max_k <= STK_LOAD_MAX_K, "stk_load_plan_create: %d time points per call (1..%d)", max_k,
                 STK_LOAD_MAX_K);
+    if (int rc = p1_check_mesh("stk_load_plan_create", d, nv, nc, points, cells)) return rc;
     const int64_t ns = (int64_t)(d + 1) * nc;
-    STK_REQUIRE(nv < ((int64_t)1 << 31) && ns < ((int64_t)1 << 31), "stk_load_plan_create: mesh too large for 32-bit tables");
-    for (int64_t q = 0; q < ns; ++q)
-        STK_REQUIRE(cells[q] >= 0 && cells[q] < nv, "stk_load_plan_create: cell %lld names vertex %lld",
-                    (long long)(q / (d + 1)), (long long)cells[q]);
     for (int64_t i = 0; i < n_free; ++i)
         STK_REQUIRE(free_vertices[i] >= 0 && free_vertices[i] < nv, "stk_load_plan_create: free dof %lld is vertex %lld",
                     (long long)i, (long long)free_vertices[i]);
@@ -262,17 +184,13 @@ extern "C" int stk_load_plan_create(int32_t d, int64_t nv, int64_t nc, const dou
         const int64_t v = free_vertices[i];
         std::copy(slot.begin() + start[v], slot.begin() + start[v + 1], inc_slot.begin() + inc_ptr[i]);
     }
-    std::vector<int32_t> cells32((size_t)ns);
-    for (int64_t q = 0; q < ns; ++q) cells32[q] = (int32_t)cells[q];
-    std::vector<double> pts(points, points + nv * d);
 
     stk_load_plan *p = new stk_load_plan();
     p->d = d, p->max_k = max_k, p->nv = nv, p->nc = nc, p->n_free = n_free, p->ns = ns;
-    int rc = upload(&p->points, pts);
-    if (!rc) rc = upload(&p->cells, cells32);
-    if (!rc) rc = upload(&p->inc_ptr, inc_ptr);
-    if (!rc) rc = upload(&p->inc_slot, inc_slot);
-    if (!rc && row_order) rc = upload(&p->order, order);
+    int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, cells, nullptr);
+    if (!rc) rc = p1_upload(&p->inc_ptr, inc_ptr.data(), inc_ptr.size());
+    if (!rc) rc = p1_upload(&p->inc_slot, inc_slot.data(), inc_slot.size());
+    if (!rc && row_order) rc = p1_upload(&p->order, order.data(), order.size());
     if (rc) {
         release(p);
         return rc;
@@ -282,9 +200,9 @@ extern "C" int stk_load_plan_create(int32_t d, int64_t nv, int64_t nc, const dou
     if (e == hipSuccess) {
         const dim3 grid(stk_flat_grid(nc, BS));
         if (d == 2)
-            hipLaunchKernelGGL(load_volume_kernel<2>, grid, dim3(BS), 0, 0, nc, p->points, p->cells, p->vol);
+            hipLaunchKernelGGL(load_volume_kernel<2>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol);
         else
-            hipLaunchKernelGGL(load_volume_kernel<3>, grid, dim3(BS), 0, 0, nc, p->points, p->cells, p->vol);
+            hipLaunchKernelGGL(load_volume_kernel<3>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -308,17 +226,7 @@ extern "C" int stk_load_points(void *stream, const stk_load_plan *plan, int32_t 
 {
     const stk_timed timed_(STK_OP_SPACE, stream);
     STK_REQUIRE(plan && q_points, "stk_load_points: null pointer");
-    load_rule r = {};
-    if (int rc = fill_rule("stk_load_points", plan, nq, nullptr, rule_points, &r)) return rc;
-    const int64_t total = plan->nc * nq;
-    const dim3 grid(stk_flat_grid(total, BS));
-    hipStream_t st = stk_stream(stream);
-    if (plan->d == 2)
-        hipLaunchKernelGGL(load_points_kernel<2>, grid, dim3(BS), 0, st, total, nq, plan->points, plan->cells, r, q_points);
-    else
-        hipLaunchKernelGGL(load_points_kernel<3>, grid, dim3(BS), 0, st, total, nq, plan->points, plan->cells, r, q_points);
-    STK_LAUNCH_CHECK();
-    return 0;
+    return p1_points("stk_load_points", stream, plan, nq, rule_points, q_points);
 }
 
 extern "C" int stk_load_columns(void *stream, const stk_load_plan *plan, int32_t nq, const double *rule_weights,
@@ -330,8 +238,8 @@ extern "C" int stk_load_columns(void *stream, const stk_load_plan *plan, int32_t
     STK_REQUIRE(n_k >= 1 && n_k <= plan->max_k, "stk_load_columns: %d time points on a plan made for %d", n_k, plan->max_k);
     STK_REQUIRE(ld >= 2 && (ld & 1) == 0 && (((uintptr_t)out_pair) & 15) == 0,
                 "stk_load_columns: the column pair must be 16-byte aligned in a slab of even leading dimension (ld=%d)", ld);
-    load_rule r = {};
-    if (int rc = fill_rule("stk_load_columns", plan, nq, rule_weights, rule_points, &r)) return rc;
+    p1_rule r = {};
+    if (int rc = p1_fill_rule("stk_load_columns", plan->d, nq, rule_weights, rule_points, &r)) return rc;
     load_coef c = {};
     for (int k = 0; k < 2 * n_k; ++k) c.c[k] = coef[k];
     hipStream_t st = stk_stream(stream);

@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "host_threads.h"
 #include "stk_common.h"
 
 #pragma clang fp contract(off)
@@ -40,29 +41,6 @@ inline bool before(const EdgeKey &a, const EdgeKey &b)
     if (a.x != b.x) return a.x < b.x;
     return a.e < b.e;  // lexsort is stable
 }
-
-int host_threads(int64_t items)
-{
-    int T = (int)std::thread::hardware_concurrency();
-    if (const char *env = getenv("STK_HOST_THREADS")) T = atoi(env);
-    T = std::max(1, std::min(T, 32));
-    if (items < 16384) T = 1;
-    return T;
-}
-
-template <class F>
-void on_threads(int T, F body)
-{
-    if (T == 1) {
-        body(0);
-        return;
-    }
-    std::vector<std::thread> pool;
-    for (int k = 0; k < T; ++k) pool.emplace_back(body, k);
-    for (auto &th : pool) th.join();
-}
-
-inline int64_t share(int64_t n, int T, int k) { return n * k / T; }
 
 // keys[0 .. n) into ascending order: samples pick T - 1 splitters, every thread
 // scatters its share into the buckets and then sorts one bucket

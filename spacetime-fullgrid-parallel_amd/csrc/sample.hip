@@ -7,13 +7,15 @@
 //                           On the host threads of the library; no GPU touched.
 //  * stk_sample_plan_create uploads the mesh, the vertex -> slab-row map and that grid
 //  * stk_sample_locate      one lane per point: the cells of the point's bin, barycentric
-//                           coordinates by the signed-area / cofactor expressions, the
-//                           cell with the largest smallest coordinate
+//                           coordinates by the signed-area / cofactor expressions
+//                           (p1_barycentric, p1_mesh.h), the cell with the largest smallest
+//                           coordinate
 //  * stk_sample_eval        out[k][p] = w0 s_p(c0) + w1 s_p(c1) with the spatial sums
 //                           s_p(c) = ((l0 u[v0][c] + l1 u[v1][c]) + l2 u[v2][c]) [+ ...]
 //  * stk_sample_pairs       paired requests (t_p, x_p): one lane per point, u_h, its time
 //                           derivative and its gradient from 2 (d + 1) slab entries
-//  * stk_sample_grad_coeffs the gradients of the barycentric coordinates per located point:
+//  * stk_sample_grad_coeffs the gradients of the barycentric coordinates (p1_gradients,
+//                           p1_mesh.h) per located point:
 //                           as `lam` of stk_sample_eval they give the blocks of the gradient
 //  * stk_sample_pairs_adjoint  E^T of the pairs: numbers at (t_p, x_p) onto the slab, as
 //                           store, stable sort by destination (sample_adj_sort.hip) and one
@@ -31,16 +33,13 @@
 // requests read it.  No atomics; every sum has one owner and one order.
 //
 // ARITHMETIC: every product and every sum rounded on its own -- contraction is SWITCHED
-// OFF for this file (the pragma below and -ffp-contract=off in the Makefile), as for the
-// load engine, and no kernel here calls fma.
+// OFF for this file and for p1_mesh.h (their pragmas and -ffp-contract=off in the Makefile), as
+// for the load engine, and no kernel here calls fma.
 #include <algorithm>
-#include <cmath>
-#include <cstdlib>
-#include <thread>
-#include <vector>
 
+#include "host_threads.h"
+#include "p1_mesh.h"
 #include "sample_adj_sort.h"
-#include "stk_common.h"
 
 #pragma clang fp contract(off)
 
@@ -76,77 +75,6 @@ __host__ __device__ inline int32_t bin_of(double x, double lo, double inv_w, int
     return (int32_t)t;
 }
 
-int host_threads(int64_t items)
-{
-    int T = (int)std::thread::hardware_concurrency();
-    if (const char *env = getenv("STK_HOST_THREADS")) T = atoi(env);
-    T = std::max(1, std::min(T, 32));
-    if (items < 16384) T = 1;
-    return T;
-}
-
-template <class F>
-void on_threads(int T, F body)
-{
-    if (T == 1) {
-        body(0);
-        return;
-    }
-    std::vector<std::thread> pool;
-    for (int k = 0; k < T; ++k) pool.emplace_back(body, k);
-    for (auto &th : pool) th.join();
-}
-
-inline int64_t share(int64_t n, int T, int k) { return n * k / T; }
-
-int check_mesh(const char *who, int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells)
-{
-    STK_REQUIRE((d == 2 || d == 3) && nv > 0 && nc > 0 && points && cells, "%s: bad arguments", who);
-    STK_REQUIRE(nv < ((int64_t)1 << 31) && (int64_t)(d + 1) * nc < ((int64_t)1 << 31), "%s: mesh too large for 32-bit tables",
-                who);
-    for (int64_t q = 0; q < (int64_t)(d + 1) * nc; ++q)
-        STK_REQUIRE(cells[q] >= 0 && cells[q] < nv, "%s: cell %lld names vertex %lld", who, (long long)(q / (d + 1)),
-                    (long long)cells[q]);
-    return 0;
-}
-
-// ---- barycentric coordinates -----------------------------------------------------------
-// triangles: signed areas over the signed area of the cell; tetrahedra: the cofactors of
-// the edge matrix (cross products) over its determinant, every dot product summed from the
-// left; l0 = ((1 - l1) - l2) [- l3].  A vertex of the cell gets exactly (1, 0, 0) there.
-template <int D>
-__device__ inline void barycentric(const double *__restrict__ pts, const int32_t *__restrict__ c, const double *x,
-                                   double *l)
-{
-    const double *p0 = pts + D * (int64_t)c[0];
-    double e[D][D], q[D];
-#pragma unroll
-    for (int r = 0; r < D; ++r)
-#pragma unroll
-        for (int k = 0; k < D; ++k) e[r][k] = pts[D * (int64_t)c[r + 1] + k] - p0[k];
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[k] = x[k] - p0[k];
-    if constexpr (D == 2) {
-        const double det = e[0][0] * e[1][1] - e[0][1] * e[1][0];
-        l[1] = (q[0] * e[1][1] - q[1] * e[1][0]) / det;
-        l[2] = (e[0][0] * q[1] - e[0][1] * q[0]) / det;
-        l[0] = (1.0 - l[1]) - l[2];
-    } else {
-        double n[3][3];  // n[0] = e1 x e2, n[1] = e2 x e0, n[2] = e0 x e1
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const double *a = e[(r + 1) % 3], *b = e[(r + 2) % 3];
-            n[r][0] = a[1] * b[2] - a[2] * b[1];
-            n[r][1] = a[2] * b[0] - a[0] * b[2];
-            n[r][2] = a[0] * b[1] - a[1] * b[0];
-        }
-        const double det = (e[0][0] * n[0][0] + e[0][1] * n[0][1]) + e[0][2] * n[0][2];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) l[r + 1] = ((q[0] * n[r][0] + q[1] * n[r][1]) + q[2] * n[r][2]) / det;
-        l[0] = ((1.0 - l[1]) - l[2]) - l[3];
-    }
-}
-
 // one lane per point
 template <int D>
 __global__ __launch_bounds__(BS) void sample_locate_kernel(int64_t n_p, const double *__restrict__ x, grid_desc g,
@@ -174,7 +102,7 @@ __global__ __launch_bounds__(BS) void sample_locate_kernel(int64_t n_p, const do
         for (int32_t s = begin; s < end; ++s) {  // ascending cells: `>` keeps the lowest on a tie
             const int32_t t = bin_cells[s];
             double l[D + 1];
-            barycentric<D>(pts, cells + (D + 1) * (int64_t)t, xp, l);
+            p1_barycentric(p1_simplex_of<D>(pts, cells + (D + 1) * (int64_t)t), xp, l);
             double m = l[0];
 #pragma unroll
             for (int a = 1; a <= D; ++a) m = l[a] < m ? l[a] : m;
@@ -279,45 +207,6 @@ __global__ __launch_bounds__(BS) void sample_eval_kernel(int64_t n_p, int64_t nc
     }
 }
 
-// ---- gradients of the barycentric coordinates ---------------------------------------------
-// G[a][j] = d_j l_a of a cell, from the edge vectors, determinant and cross products that
-// barycentric() above forms: every quotient rounded once,
-// G[0] = ((0 - G[1]) - G[2]) [- G[3]].  Evaluated per point in the kernels below; the plan
-// holds no table, so its construction is what it was.
-template <int D>
-__device__ inline void barycentric_gradients(const double *__restrict__ pts, const int32_t *v, double (*G)[D])
-{
-    const double *p0 = pts + D * (int64_t)v[0];
-    double e[D][D];
-#pragma unroll
-    for (int r = 0; r < D; ++r)
-#pragma unroll
-        for (int k = 0; k < D; ++k) e[r][k] = pts[D * (int64_t)v[r + 1] + k] - p0[k];
-    if constexpr (D == 2) {
-        const double det = e[0][0] * e[1][1] - e[0][1] * e[1][0];
-        G[1][0] = e[1][1] / det, G[1][1] = (-e[1][0]) / det;
-        G[2][0] = (-e[0][1]) / det, G[2][1] = e[0][0] / det;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) G[0][j] = (0.0 - G[1][j]) - G[2][j];
-    } else {
-        double n[3][3];  // n[0] = e1 x e2, n[1] = e2 x e0, n[2] = e0 x e1
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const double *a = e[(r + 1) % 3], *b = e[(r + 2) % 3];
-            n[r][0] = a[1] * b[2] - a[2] * b[1];
-            n[r][1] = a[2] * b[0] - a[0] * b[2];
-            n[r][2] = a[0] * b[1] - a[1] * b[0];
-        }
-        const double det = (e[0][0] * n[0][0] + e[0][1] * n[0][1]) + e[0][2] * n[0][2];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) G[r + 1][j] = n[r][j] / det;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) G[0][j] = ((0.0 - G[1][j]) - G[2][j]) - G[3][j];
-    }
-}
-
 // one lane per point: out [D][n_p][D + 1], the coefficients stk_sample_eval takes as `lam`
 template <int D>
 __global__ __launch_bounds__(BS) void sample_grad_coeffs_kernel(int64_t n_p, int64_t nc, const int32_t *__restrict__ cell,
@@ -333,7 +222,7 @@ __global__ __launch_bounds__(BS) void sample_grad_coeffs_kernel(int64_t n_p, int
             int32_t v[D + 1];
 #pragma unroll
             for (int a = 0; a <= D; ++a) v[a] = cells[(D + 1) * (int64_t)t + a];
-            barycentric_gradients<D>(pts, v, G);
+            p1_gradients(p1_simplex_of<D>(pts, v), G);
         } else {
 #pragma unroll
             for (int a = 0; a <= D; ++a)
@@ -384,12 +273,7 @@ __global__ __launch_bounds__(BS) void sample_pairs_kernel(int64_t n_p, int64_t n
 #pragma unroll
         for (int j = 0; j < D; ++j) val_g[j] = nan;
         if (tc >= 0 && tc < nc && tp >= 0.0 && tp <= t_last) {  // a NaN time fails both comparisons
-            const double x = tp / h;
-            double ef = floor(x);
-            if (ef > (double)(N - 2)) ef = (double)(N - 2);
-            const double w1 = x - ef, w0 = 1.0 - w1;
-            const int64_t c0 = (int64_t)ef - t_begin, c1 = c0 + 1;
-            const bool have0 = c0 >= 0 && c0 < n_loc, have1 = c1 >= 0 && c1 < n_loc;
+            const auto [w0, w1, c0, c1, have0, have1] = p1_time_bracket(tp, h, N, t_begin, n_loc);
             int32_t v[D + 1], r[D + 1];
 #pragma unroll
             for (int a = 0; a <= D; ++a) v[a] = cells[(D + 1) * (int64_t)tc + a];
@@ -417,7 +301,7 @@ __global__ __launch_bounds__(BS) void sample_pairs_kernel(int64_t n_p, int64_t n
                 for (int a = 0; a <= D; ++a)
                     if (r[a] < 0) u0[a] = u1[a] = 0.0;
             }
-            if (want_grad) barycentric_gradients<D>(pts, v, G);
+            if (want_grad) p1_gradients(p1_simplex_of<D>(pts, v), G);
             if (want_u || want_dt) {
                 const double s0 = spatial_sum<D>(l, u0), s1 = spatial_sum<D>(l, u1);
                 const double a0 = have0 ? w0 * s0 : 0.0, a1 = have1 ? w1 * s1 : 0.0;
@@ -480,18 +364,13 @@ __global__ __launch_bounds__(BS) void sample_adj_records_kernel(
 #pragma unroll
         for (int k = 0; k < K; ++k) key[k] = none, term[k] = 0.0;
         if (ok) {
-            const double x = tp / h;
-            double ef = floor(x);
-            if (ef > (double)(N - 2)) ef = (double)(N - 2);
-            const double w1 = x - ef, w0 = 1.0 - w1;
-            const int64_t c0 = (int64_t)ef - t_begin, c1 = c0 + 1;
-            const bool have0 = c0 >= 0 && c0 < n_loc, have1 = c1 >= 0 && c1 < n_loc;
+            const auto [w0, w1, c0, c1, have0, have1] = p1_time_bracket(tp, h, N, t_begin, n_loc);
             int32_t v[D + 1];
 #pragma unroll
             for (int b = 0; b <= D; ++b) v[b] = cells[(D + 1) * (int64_t)tc + b];
             if (field == 4) {
                 double G[D + 1][D], wj[D];
-                barycentric_gradients<D>(pts, v, G);
+                p1_gradients(p1_simplex_of<D>(pts, v), G);
 #pragma unroll
                 for (int j = 0; j < D; ++j) wj[j] = w[j * ld_w + p];
 #pragma unroll
@@ -617,23 +496,13 @@ int adj_layout(int64_t n_p, int32_t d, size_t *part, size_t *sort_bytes, size_t 
     return 0;
 }
 
-template <typename T>
-int upload(T **dst, const T *src, size_t n)
-{
-    STK_HIP(hipMalloc((void **)dst, (n ? n : 1) * sizeof(T)));
-    if (n) STK_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
 }  // namespace
 
 struct stk_sample_plan {
     int32_t d;
     int64_t nv, nc, n_free;
     grid_desc g;
-    double *points;      // [nv][d]
-    int32_t *cells;      // [nc][d + 1]
-    int32_t *row_of;     // [nv]: slab row of a vertex, -1 on the boundary
+    p1_mesh_dev mesh;
     int32_t *bin_ptr;    // [bins + 1]
     int32_t *bin_cells;  // cells of bin b: bin_ptr[b] .. bin_ptr[b + 1], ascending
     // request tables of stk_sample_eval: written into pinned host memory, copied on the
@@ -649,7 +518,8 @@ namespace {
 void release(stk_sample_plan *p)
 {
     if (!p) return;
-    void *arrays[] = {p->points, p->cells, p->row_of, p->bin_ptr, p->bin_cells, p->req_dev};
+    p1_mesh_free(&p->mesh);
+    void *arrays[] = {p->bin_ptr, p->bin_cells, p->req_dev};
     for (void *a : arrays)
         if (a) (void)hipFree(a);
     if (p->req_host) (void)hipHostFree(p->req_host);
@@ -663,7 +533,7 @@ extern "C" int stk_sample_grid_build(int32_t d, int64_t nv, int64_t nc, const do
                                      stk_sample_grid **out)
 {
     STK_REQUIRE(out, "stk_sample_grid_build: null pointer");
-    if (int rc = check_mesh("stk_sample_grid_build", d, nv, nc, points, cells)) return rc;
+    if (int rc = p1_check_mesh("stk_sample_grid_build", d, nv, nc, points, cells)) return rc;
     double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     for (int k = 0; k < d; ++k) lo[k] = hi[k] = points[k];
     for (int64_t v = 0; v < nv; ++v)
@@ -778,28 +648,18 @@ extern "C" int stk_sample_plan_create(int32_t d, int64_t nv, int64_t nc, const d
     STK_REQUIRE(out && n_free > 0 && free_vertices, "stk_sample_plan_create: bad arguments");
     stk_sample_grid *grid = nullptr;
     if (int rc = stk_sample_grid_build(d, nv, nc, points, cells, &grid)) return rc;
-    std::vector<int32_t> row_of((size_t)nv, -1);
-    for (int64_t i = 0; i < n_free; ++i) {
-        const int64_t v = free_vertices[i];
-        if (!(v >= 0 && v < nv && row_of[(size_t)v] < 0 && n_free < ((int64_t)1 << 31))) {
-            stk_sample_grid_free(grid);
-            stk_set_error("stk_sample_plan_create: free dof %lld is vertex %lld (out of range or named twice)", (long long)i,
-                          (long long)v);
-            return 2;
-        }
-        row_of[(size_t)v] = (int32_t)i;
+    std::vector<int32_t> row_of;
+    if (int rc = p1_row_of("stk_sample_plan_create", nv, n_free, free_vertices, &row_of)) {
+        stk_sample_grid_free(grid);
+        return rc;
     }
-    std::vector<int32_t> cells32((size_t)(d + 1) * nc);
-    for (size_t q = 0; q < cells32.size(); ++q) cells32[q] = (int32_t)cells[q];
 
     stk_sample_plan *p = new stk_sample_plan();
     p->d = d, p->nv = nv, p->nc = nc, p->n_free = n_free;
     for (int k = 0; k < 3; ++k) p->g.nb[k] = grid->nb[k], p->g.lo[k] = grid->lo[k], p->g.inv_w[k] = grid->inv_w[k];
-    int rc = upload(&p->points, points, (size_t)nv * d);
-    if (!rc) rc = upload(&p->cells, cells32.data(), cells32.size());
-    if (!rc) rc = upload(&p->row_of, row_of.data(), row_of.size());
-    if (!rc) rc = upload(&p->bin_ptr, grid->bin_ptr.data(), grid->bin_ptr.size());
-    if (!rc) rc = upload(&p->bin_cells, grid->bin_cells.data(), grid->bin_cells.size());
+    int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, cells, &row_of);
+    if (!rc) rc = p1_upload(&p->bin_ptr, grid->bin_ptr.data(), grid->bin_ptr.size());
+    if (!rc) rc = p1_upload(&p->bin_cells, grid->bin_cells.data(), grid->bin_cells.size());
     stk_sample_grid_free(grid);
     if (!rc && hipEventCreateWithFlags(&p->copied, hipEventDisableTiming) != hipSuccess) {
         stk_set_error("stk_sample_plan_create: no event");
@@ -829,10 +689,10 @@ extern "C" int stk_sample_locate(void *stream, const stk_sample_plan *plan, int6
     hipStream_t st = stk_stream(stream);
     if (plan->d == 2)
         hipLaunchKernelGGL(sample_locate_kernel<2>, grid, dim3(BS), 0, st, n_p, x, plan->g, plan->bin_ptr, plan->bin_cells,
-                           plan->points, plan->cells, cell, lam);
+                           plan->mesh.points, plan->mesh.cells, cell, lam);
     else
         hipLaunchKernelGGL(sample_locate_kernel<3>, grid, dim3(BS), 0, st, n_p, x, plan->g, plan->bin_ptr, plan->bin_cells,
-                           plan->points, plan->cells, cell, lam);
+                           plan->mesh.points, plan->mesh.cells, cell, lam);
     STK_LAUNCH_CHECK();
     return 0;
 }
@@ -922,10 +782,10 @@ extern "C" int stk_sample_eval(void *stream, stk_sample_plan *plan, int64_t n_p,
         const double *w = (const double *)(plan->req_dev + L.off_w);
         double *o = out + (int64_t)L.k0 * ld_out;
         if (d == 2)
-            hipLaunchKernelGGL(sample_eval_kernel<2>, grid, dim3(BS), lds, st, n_p, plan->nc, cell, lam, plan->cells, plan->row_of, ld,
+            hipLaunchKernelGGL(sample_eval_kernel<2>, grid, dim3(BS), lds, st, n_p, plan->nc, cell, lam, plan->mesh.cells, plan->mesh.row_of, ld,
                                slab, L.n_c, cols, L.n_kc, req, w, ld_out, o);
         else
-            hipLaunchKernelGGL(sample_eval_kernel<3>, grid, dim3(BS), lds, st, n_p, plan->nc, cell, lam, plan->cells, plan->row_of, ld,
+            hipLaunchKernelGGL(sample_eval_kernel<3>, grid, dim3(BS), lds, st, n_p, plan->nc, cell, lam, plan->mesh.cells, plan->mesh.row_of, ld,
                                slab, L.n_c, cols, L.n_kc, req, w, ld_out, o);
         STK_LAUNCH_CHECK();
     }
@@ -941,10 +801,10 @@ extern "C" int stk_sample_grad_coeffs(void *stream, const stk_sample_plan *plan,
     const dim3 grid(stk_flat_grid(n_p, BS));
     hipStream_t st = stk_stream(stream);
     if (plan->d == 2)
-        hipLaunchKernelGGL(sample_grad_coeffs_kernel<2>, grid, dim3(BS), 0, st, n_p, plan->nc, cell, plan->points, plan->cells,
+        hipLaunchKernelGGL(sample_grad_coeffs_kernel<2>, grid, dim3(BS), 0, st, n_p, plan->nc, cell, plan->mesh.points, plan->mesh.cells,
                            out);
     else
-        hipLaunchKernelGGL(sample_grad_coeffs_kernel<3>, grid, dim3(BS), 0, st, n_p, plan->nc, cell, plan->points, plan->cells,
+        hipLaunchKernelGGL(sample_grad_coeffs_kernel<3>, grid, dim3(BS), 0, st, n_p, plan->nc, cell, plan->mesh.points, plan->mesh.cells,
                            out);
     STK_LAUNCH_CHECK();
     return 0;
@@ -970,7 +830,7 @@ extern "C" int stk_sample_pairs(void *stream, const stk_sample_plan *plan, int64
     hipStream_t st = stk_stream(stream);
 #define STK_PAIRS(D, W)                                                                                                     \
     hipLaunchKernelGGL((sample_pairs_kernel<D, W>), grid, dim3(BS), 0, st, n_p, plan->nc, cell, lam, t, h, t_last, N, t_begin, \
-                       n_loc, ld, slab, plan->points, plan->cells, plan->row_of, fields, ld_out, out)
+                       n_loc, ld, slab, plan->mesh.points, plan->mesh.cells, plan->mesh.row_of, fields, ld_out, out)
     if (plan->d == 2) {
         if (wide) STK_PAIRS(2, true);
         else STK_PAIRS(2, false);
@@ -1033,10 +893,10 @@ extern "C" int stk_sample_pairs_adjoint(void *stream, const stk_sample_plan *pla
     const dim3 grid(stk_flat_grid(n_p, BS));
     if (plan->d == 2)
         hipLaunchKernelGGL(sample_adj_records_kernel<2>, grid, dim3(BS), 0, st, n_p, plan->nc, cell, lam, t, h, t_last, N, t_begin,
-                           n_loc, none, w, ld_w, field, plan->points, plan->cells, plan->row_of, keys[0], vals[0], used);
+                           n_loc, none, w, ld_w, field, plan->mesh.points, plan->mesh.cells, plan->mesh.row_of, keys[0], vals[0], used);
     else
         hipLaunchKernelGGL(sample_adj_records_kernel<3>, grid, dim3(BS), 0, st, n_p, plan->nc, cell, lam, t, h, t_last, N, t_begin,
-                           n_loc, none, w, ld_w, field, plan->points, plan->cells, plan->row_of, keys[0], vals[0], used);
+                           n_loc, none, w, ld_w, field, plan->mesh.points, plan->mesh.cells, plan->mesh.row_of, keys[0], vals[0], used);
     STK_LAUNCH_CHECK();
     int half = 0;
     if (int rc = stk_adj_sort(st, base + 4 * part, adj_align(sort_bytes), keys, vals, n_rec, key_bits, &half)) return rc;

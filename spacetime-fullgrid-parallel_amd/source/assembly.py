@@ -441,32 +441,18 @@ class DeviceLoadPlan:
     the free dofs (M_x.stk_row_order), a performance hint.  Not for two streams at once:
     the plan owns the workspace of `columns()`."""
     def __init__(self, mesh, max_k=4, row_order=None):
-        import ctypes
-
-        import torch
-
         from . import _lib
+        from .p1_plan import MeshPlanHandle
         self._lib = _lib
-        self.d = mesh.cells.shape[1] - 1
-        self.nc, self.max_k = len(mesh.cells), max_k
+        self.max_k = max_k
         self.qw, self.ql = (np.ascontiguousarray(a, dtype=np.float64) for a in simplex_rule(mesh))
-        pts = np.ascontiguousarray(mesh.points, dtype=np.float64)
-        cells = np.ascontiguousarray(mesh.cells, dtype=np.int64)
-        fd = np.ascontiguousarray(free_dofs(mesh), dtype=np.int64)
-        self.n_free = len(fd)
         order = None if row_order is None else np.ascontiguousarray(row_order, dtype=np.int32)
-        assert order is None or order.shape == (self.n_free,)
-        self._plan = ctypes.c_void_p()
+        assert order is None or order.shape == (len(free_dofs(mesh)),)
         self._points = None
-        with torch.cuda.device(_lib.compute_device()):
-            _lib.check(_lib.lib().stk_load_plan_create(
-                self.d, mesh.nv, self.nc, pts.ctypes.data, cells.ctypes.data, self.n_free, fd.ctypes.data,
-                None if order is None else order.ctypes.data, max_k, ctypes.byref(self._plan)))
-
-    def __del__(self):
-        if getattr(self, '_plan', None):
-            self._lib.lib().stk_load_plan_destroy(self._plan)
-            self._plan = None
+        order_ptr = None if order is None else order.ctypes.data
+        self._plan = MeshPlanHandle(mesh, lambda lib, m, out: lib.stk_load_plan_create(*m, order_ptr, max_k, out),
+                                    lambda lib, plan: lib.stk_load_plan_destroy(plan))
+        self.d, self.nc, self.n_free = self._plan.d, self._plan.nc, self._plan.n_free
 
     def points(self, ql=None):
         """Device tensor (d, nc, nq): coordinate k of quadrature point q of cell t; of

@@ -21,9 +21,9 @@ discretisation error it measures.
 Scope: vectors of the TRIAL space.  The H^1(I; H^-1) part of the X-norm and test-space
 vectors are not served.
 """
-import ctypes
-
 import numpy as np
+
+from .p1_plan import MeshPlanHandle
 
 
 def element_owner(N, t_begin, t_end):
@@ -38,31 +38,15 @@ class ErrorPlan:
     """The error-norm engine of libstk on one mesh.  Not for two streams at once: the
     plan owns the tile partials of a call in flight."""
     def __init__(self, mesh, mesh_time):
-        import torch
-
         from . import _lib
-        from .assembly import free_dofs, simplex_rule
+        from .assembly import simplex_rule
         self._lib = _lib
         self.mesh_time = mesh_time
-        pts = np.ascontiguousarray(mesh.points, dtype=np.float64)
-        cells = np.ascontiguousarray(mesh.cells, dtype=np.int64)
-        self.d, self.nc = cells.shape[1] - 1, len(cells)
-        fd = np.ascontiguousarray(free_dofs(mesh), dtype=np.int64)
-        self.n_free = len(fd)
         self.qw, self.ql = (np.ascontiguousarray(a, dtype=np.float64) for a in simplex_rule(mesh))
         self._points = None
-        self._plan = ctypes.c_void_p()
-        # the library held by the closure: __del__ may run at interpreter exit
-        self._destroy = lambda plan, lib=_lib.lib(): lib.stk_err_plan_destroy(plan)
-        with torch.cuda.device(_lib.compute_device()):
-            _lib.check(_lib.lib().stk_err_plan_create(
-                self.d, len(pts), self.nc, pts.ctypes.data, cells.ctypes.data, self.n_free, fd.ctypes.data,
-                ctypes.byref(self._plan)))
-
-    def __del__(self):
-        if getattr(self, '_plan', None):
-            self._destroy(self._plan)
-            self._plan = None
+        self._plan = MeshPlanHandle(mesh, lambda lib, m, out: lib.stk_err_plan_create(*m, out),
+                                    lambda lib, plan: lib.stk_err_plan_destroy(plan))
+        self.d, self.nc, self.n_free = self._plan.d, self._plan.nc, self._plan.n_free
 
     def points(self, ql=None):
         """Device tensor (d, nc, nq): coordinate k of quadrature point q of cell t; of the

@@ -29,11 +29,7 @@ import ctypes
 
 import numpy as np
 
-
-def _mesh_arrays(mesh):
-    pts = np.ascontiguousarray(mesh.points, dtype=np.float64)
-    cells = np.ascontiguousarray(mesh.cells, dtype=np.int64)
-    return pts, cells, cells.shape[1] - 1
+from .p1_plan import MeshPlanHandle, mesh_arrays
 
 
 def bucket_grid(mesh):
@@ -42,7 +38,7 @@ def bucket_grid(mesh):
     inv_width (d,), widen, bin_ptr, bin_cells (CSR: the cells of bin
     ``(iz bins[1] + iy) bins[0] + ix`` in ascending order)."""
     from . import _lib
-    pts, cells, d = _mesh_arrays(mesh)
+    pts, cells, d = mesh_arrays(mesh)
     lib, grid = _lib.lib(), ctypes.c_void_p()
     _lib.check(lib.stk_sample_grid_build(d, len(pts), len(cells), pts.ctypes.data, cells.ctypes.data,
                                          ctypes.byref(grid)))
@@ -109,27 +105,12 @@ class SamplePlan:
     is what source/problem.py builds).  Not for two streams at once: the plan owns the
     request tables of a call in flight."""
     def __init__(self, mesh, mesh_time=None):
-        import torch
-
         from . import _lib
-        from .assembly import free_dofs
         self._lib = _lib
         self.mesh_time = mesh_time
-        pts, cells, self.d = _mesh_arrays(mesh)
-        fd = np.ascontiguousarray(free_dofs(mesh), dtype=np.int64)
-        self.n_free = len(fd)
-        self._plan = ctypes.c_void_p()
-        # the library held by the closure: __del__ may run at interpreter exit
-        self._destroy = lambda plan, lib=_lib.lib(): lib.stk_sample_plan_destroy(plan)
-        with torch.cuda.device(_lib.compute_device()):
-            _lib.check(_lib.lib().stk_sample_plan_create(
-                self.d, len(pts), len(cells), pts.ctypes.data, cells.ctypes.data, self.n_free, fd.ctypes.data,
-                ctypes.byref(self._plan)))
-
-    def __del__(self):
-        if getattr(self, '_plan', None):
-            self._destroy(self._plan)
-            self._plan = None
+        self._plan = MeshPlanHandle(mesh, lambda lib, m, out: lib.stk_sample_plan_create(*m, out),
+                                    lambda lib, plan: lib.stk_sample_plan_destroy(plan))
+        self.d, self.n_free = self._plan.d, self._plan.n_free
 
     def locate(self, points):
         """points: (n_p, d) NumPy array or device tensor (or what locate returned)."""

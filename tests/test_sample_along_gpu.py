@@ -229,6 +229,22 @@ def test_no_points_and_an_odd_leading_dimension():
         assert np.max(np.abs(G[:, inside] - oracle.transpose(2, 0, 1))) <= DERIV_TOL * np.max(np.abs(oracle))
 
 
+@pytest.mark.parametrize('problem,J', [('square', 1), ('square', 2), ('lshape', 1), ('cube', 1)])
+def test_grad_coeffs_are_the_gradients_of_the_assembly(problem, J):
+    """At the centroid of every cell, stk_sample_grad_coeffs gives the doubles of
+    assembly._simplex_geometry -- what the error norms and the stiffness matrix use -- and
+    not merely close ones.  (array_equal does not tell -0.0 from +0.0: grad lambda_0 is
+    ((0 - g_1) - g_2) [- g_3] here and -((g_1 + g_2) [+ g_3]) there.)"""
+    from source.assembly import _simplex_geometry
+    mesh, plan = mesh_of(problem, J), plan_of(problem, J)
+    loc = plan.locate(point_sets(problem, J)['centroids'])
+    assert np.array_equal(loc.cell.cpu().numpy(), np.arange(len(mesh.cells)))
+    G = plan.grad_coeffs(loc).cpu().numpy()  # [j, cell, a]
+    want = _simplex_geometry(mesh)[1]  # [cell, a, j]
+    assert G.shape == want.transpose(2, 0, 1).shape and np.isfinite(want).all()
+    assert np.array_equal(G, want.transpose(2, 0, 1))
+
+
 # ---- 4. rank independence ----------------------------------------------------------------------------
 _lock = threading.Lock()  # plan construction reads process-wide tuning keys
 
