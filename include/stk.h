@@ -645,7 +645,12 @@ typedef struct {
     int32_t diag_free;
 } stk_ell_rows;
 
-/* y = alpha * A(t) x + beta * z; x has x_rows rows, y and z have ell->n_rows. */
+/* y = alpha * A(t) x + beta * z; x has x_rows rows, y and z have ell->n_rows.
+ * ld must be even, n_loc at most 1024, the slabs 16-byte aligned.  A call writes the columns
+ * 0 .. 2*ceil(n_loc/2) - 1 of the listed rows of y and nothing else: the padding column of an
+ * odd n_loc is written as +0.0 whatever x and z hold there (their padding is read with its
+ * pair and discarded), and the columns from there to ld -- the slab as a column range of a
+ * wider one -- are neither read nor written.  A refused call writes nothing. */
 int stk_ell_spmm(void *stream, const stk_ell_rows *ell_host, int32_t n_loc,
                  int32_t ld, int32_t x_rows, double ca, const double *cm,
                  const double *x, double alpha, double beta, const double *z,
@@ -903,7 +908,12 @@ int stk_mg_destroy(stk_mg *mg);
  * does). */
 int stk_mg_set_option(stk_mg *plan, const char *key, int32_t value);
 /* u = MG(f): `vcycles` V-cycles from u = 0.  cm/kind: per-time-slice mass
- * coefficient and coarse-inverse index (device, n_loc) or NULL. */
+ * coefficient and coarse-inverse index (device, n_loc) or NULL.  u need not be
+ * initialised.  With an even ld the columns 0 .. 2*ceil(n_loc/2) - 1 of u are written (the
+ * padding column of an odd n_loc as +0.0, whatever f holds there) and the columns behind
+ * them -- the slab as a column range of a wider one -- are neither read nor written, in f
+ * or in u.  With an odd ld (the flat kernels, which know no pairs) every column of u from
+ * n_loc to ld - 1 is written as +0.0, as by stk_csr_spmm. */
 int stk_mg_apply(stk_mg *mg, void *stream, int32_t n_loc, int32_t ld,
                  double ca, const double *cm, const int32_t *kind,
                  const double *f, double *u);
@@ -921,7 +931,9 @@ int stk_mg_apply(stk_mg *mg, void *stream, int32_t n_loc, int32_t ld,
  * the index of the slice's coarse inverse).  One call per level with the n_kinds
  * matrices of that level as CSR on the host (sorted columns; a NULL indptr for a
  * kind no slice names); members take effect once every level 1..coarse_levels has
- * them.  Entries outside the plan's pattern are ignored. */
+ * them.  Entries outside the plan's pattern are ignored.  Every given matrix needs its
+ * diagonal entries; a call that is refused for a missing one leaves the plan, and members
+ * already in use, as they were. */
 int stk_mg_coarse_levels(const stk_mg *plan);
 int stk_mg_set_member_matrices(stk_mg *plan, int32_t level, int32_t n_kinds,
                                const int32_t *const *indptr_host,
@@ -946,6 +958,12 @@ int stk_mg_smooth(stk_mg *mg, void *stream, int32_t level, int32_t n_loc,
  * coords (optional, HOST): coordinates of the finest-level dofs, row-major
  * (n x dim), level l = the first n_l of them -- only used for cache-friendly row
  * orders and bands; NULL = index order / breadth-first bands.
+ * The level matrices must be structurally symmetric (a_ij stored iff a_ji is; the values
+ * may differ): the sweeps run the rows of equal depth in the dependency DAG side by side,
+ * and a row that reads a row of its own group which does not read it back would race with
+ * that row's update.  stk_mg_create_from_csr refuses a finest-level pattern (A united with
+ * M) that is not; Galerkin products of such a matrix with R = P^T are so again and are not
+ * checked, nor are the levels handed to stk_mg_create.
  * The Gauss-Seidel copies follow the tuning key "mg_gs_diag_free" AS IT STANDS WHEN
  * THE PLAN IS BUILT: 1 (default) = diagonal-free rows, u_i = (f_i - sum_{j != i}
  * a_ij u_j) / a_ii; 0 = the diagonal among the slots and the reference's update

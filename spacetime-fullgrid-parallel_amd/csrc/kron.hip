@@ -13,13 +13,14 @@
 // lanes walk t, so the gather of a CSR neighbour j is one contiguous run of
 // n_loc doubles (coalesced whatever the spatial dof order is), and the CSR
 // entries of row i are wave-broadcast loads.  HBM-bound; no MFMA.
+#include "csr_spmm.h"
 #include "stk_common.h"
 
 namespace {
 
 constexpr int SBS = 256;
 
-__global__ __launch_bounds__(SBS) void spmm_kernel(int64_t total, int32_t n_loc, int32_t ld,
+__global__ __launch_bounds__(SBS) void spmm_kernel(int64_t total, int32_t n_loc, int32_t ld, int32_t cols,
                                                    const int32_t *__restrict__ indptr,
                                                    const int32_t *__restrict__ indices,
                                                    const double *__restrict__ va, double ca,
@@ -31,8 +32,8 @@ __global__ __launch_bounds__(SBS) void spmm_kernel(int64_t total, int32_t n_loc,
     for (int64_t idx = (int64_t)blockIdx.x * SBS + threadIdx.x; idx < total; idx += stride) {
         const int row = (int)(idx / ld);
         const int t = (int)(idx - (int64_t)row * ld);
-        if (t >= n_loc) {  // padding stays zero
-            y[idx] = 0.0;
+        if (t >= n_loc) {  // padding stays zero; columns from `cols` on are not this call's
+            if (t < cols) y[idx] = 0.0;
             continue;
         }
         const int e0 = indptr[row], e1 = indptr[row + 1];
@@ -88,23 +89,32 @@ __global__ __launch_bounds__(SBS) void time_csr_kernel(int64_t total, int32_t M,
 
 }  // namespace
 
-extern "C" int stk_csr_spmm(void *stream, int32_t rows, int32_t n_loc, int32_t ld, const int32_t *indptr,
-                            const int32_t *indices, const double *vals_a, double ca, const double *vals_m,
-                            const double *cm, const double *x, double alpha, double beta, const double *z,
-                            double *y)
+// stk_csr_spmm on the first `cols` columns of the slab (csr_spmm.h).
+int stk_csr_spmm_cols(void *stream, int32_t rows, int32_t n_loc, int32_t ld, int32_t cols, const int32_t *indptr,
+                      const int32_t *indices, const double *vals_a, double ca, const double *vals_m, const double *cm,
+                      const double *x, double alpha, double beta, const double *z, double *y)
 {
     const stk_timed timed_(STK_OP_SPACE, stream);
     if (rows == 0) return 0;
-    STK_REQUIRE(rows > 0 && n_loc > 0 && ld >= n_loc, "stk_csr_spmm: bad sizes");
+    STK_REQUIRE(rows > 0 && n_loc > 0 && ld >= n_loc && cols >= n_loc && cols <= ld, "stk_csr_spmm: bad sizes");
     STK_REQUIRE(indptr && indices && vals_a && x && y, "stk_csr_spmm: null pointer");
     STK_REQUIRE((vals_m == nullptr) == (cm == nullptr), "stk_csr_spmm: vals_m and cm go together");
     STK_REQUIRE(beta == 0.0 || z, "stk_csr_spmm: beta != 0 needs z");
     STK_REQUIRE(x != y, "stk_csr_spmm: input aliases output");
     const int64_t total = (int64_t)rows * ld;
     hipLaunchKernelGGL(spmm_kernel, dim3(stk_flat_grid(total, SBS)), dim3(SBS), 0, stk_stream(stream), total,
-                       n_loc, ld, indptr, indices, vals_a, ca, vals_m, cm, x, alpha, beta, z, y);
+                       n_loc, ld, cols, indptr, indices, vals_a, ca, vals_m, cm, x, alpha, beta, z, y);
     STK_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int stk_csr_spmm(void *stream, int32_t rows, int32_t n_loc, int32_t ld, const int32_t *indptr,
+                            const int32_t *indices, const double *vals_a, double ca, const double *vals_m,
+                            const double *cm, const double *x, double alpha, double beta, const double *z,
+                            double *y)
+{
+    return stk_csr_spmm_cols(stream, rows, n_loc, ld, ld, indptr, indices, vals_a, ca, vals_m, cm, x, alpha, beta, z,
+                             y);
 }
 
 namespace {

@@ -30,6 +30,7 @@
 #include <map>
 #include <vector>
 
+#include "csr_spmm.h"
 #include "stk_common.h"
 
 namespace {
@@ -309,6 +310,10 @@ static int mgm(stk_mg *mg, hipStream_t st, int j, int n_loc, int ld, double ca, 
     double *r_j = mg->r[j], *d_c = mg->f[j - 1], *u_c = mg->u[j - 1];
     const EllLevel &E = mg->ell[j];
     const bool even = ell_slab_ok(L.n, ld);
+    // The flat kernels of a level without ELL copies keep to this call's columns like the row
+    // engine: the pair of an even ld (the padding column written as zero), every column of an
+    // odd one.
+    const int flat_cols = (ld & 1) ? ld : std::min(ld, (n_loc + 1) & ~1);
     const bool fuse_restrict = (mg->fuse_restrict >= 0 ? mg->fuse_restrict != 0 : stk_tune(g_tuning.mg_fuse_restrict) != 0) &&
                                ((j >= mg->fuse_min_level && j <= mg->fuse_max_level) || cycle < mg->fast_until_cycle ||
                                 (mg->fast_parts & 2));
@@ -338,16 +343,16 @@ static int mgm(stk_mg *mg, hipStream_t st, int j, int n_loc, int ld, double ca, 
             rc = stk_rows_ell_launch(st, 0, &E.a, 0, E.a.n_pos, n_loc, ld, L.n, L.n, ca, cm, u_j, 1.0, -1.0, f_j,
                                      r_j);
         else
-            rc = stk_csr_spmm(st, L.n, n_loc, ld, L.indptr, L.indices, L.vals_a, ca, cm ? L.vals_m : nullptr, cm,
-                              u_j, 1.0, -1.0, f_j, r_j);
+            rc = stk_csr_spmm_cols(st, L.n, n_loc, ld, flat_cols, L.indptr, L.indices, L.vals_a, ca,
+                                   cm ? L.vals_m : nullptr, cm, u_j, 1.0, -1.0, f_j, r_j);
         if (rc) return rc;
         // d_c = R r_j
         if (E.has_r && even)
             rc = stk_rows_ell_launch(st, 0, &E.r, 0, E.r.n_pos, n_loc, ld, L.n, C.n, 1.0, nullptr, r_j, 1.0, 0.0,
                                      nullptr, d_c);
         else
-            rc = stk_csr_spmm(st, C.n, n_loc, ld, L.r_indptr, L.r_indices, L.r_vals, 1.0, nullptr, nullptr, r_j,
-                              1.0, 0.0, nullptr, d_c);
+            rc = stk_csr_spmm_cols(st, C.n, n_loc, ld, flat_cols, L.r_indptr, L.r_indices, L.r_vals, 1.0, nullptr,
+                                   nullptr, r_j, 1.0, 0.0, nullptr, d_c);
         if (rc) return rc;
     }
     rc = mgm(mg, st, j - 1, n_loc, ld, ca, cm, kind, d_c, u_c, /*u_zero=*/true, cycle);
@@ -357,8 +362,8 @@ static int mgm(stk_mg *mg, hipStream_t st, int j, int n_loc, int ld, double ca, 
         rc = stk_rows_ell_launch(st, 0, &E.p, 0, E.p.n_pos, n_loc, ld, C.n, L.n, 1.0, nullptr, u_c, -1.0, 1.0, u_j,
                                  u_j);
     else
-        rc = stk_csr_spmm(st, L.n, n_loc, ld, L.p_indptr, L.p_indices, L.p_vals, 1.0, nullptr, nullptr, u_c, -1.0,
-                          1.0, u_j, u_j);
+        rc = stk_csr_spmm_cols(st, L.n, n_loc, ld, flat_cols, L.p_indptr, L.p_indices, L.p_vals, 1.0, nullptr, nullptr,
+                               u_c, -1.0, 1.0, u_j, u_j);
     if (rc) return rc;
     return smooth_level(mg, st, j, n_loc, ld, ca, cm, mg->smoothsteps, true, f_j, u_j, false, cycle);
 }

@@ -581,6 +581,20 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
                 if (u.idx[e] == i) diag[i] = e;
         for (int i = 0; i < n; ++i)
             STK_REQUIRE(diag[i] >= 0, "stk_mg_create_from_csr: level %d row %d lacks a diagonal entry", j, i);
+        if (j == J) {
+            // The sweeps run the rows of equal depth in the dependency DAG side by side: a row
+            // that reads a row which does not read it back may share its group and race with
+            // that row's update.  Checked on the caller's matrices; products R A P with
+            // R = P^T of a structurally symmetric matrix are so again.
+            for (int i = 0; i < n; ++i)
+                for (int e = u.ptr[i]; e < u.ptr[i + 1]; ++e) {
+                    const int c = u.idx[e];
+                    const int32_t *b = u.idx.data() + u.ptr[c], *t = u.idx.data() + u.ptr[c + 1];
+                    STK_REQUIRE(std::find(b, t, (int32_t)i) != t,
+                                "stk_mg_create_from_csr: the pattern is not structurally symmetric: entry (%d, %d) "
+                                "has no entry (%d, %d)", i, c, c, i);
+                }
+        }
         L.indptr = B.up(u.ptr);
         L.indices = B.up(u.idx);
         L.vals_a = B.up(u.va);

@@ -785,6 +785,20 @@ int stk_coarse_plan_set_members(stk_coarse_plan *p, int level, int n_kinds, int3
     STK_REQUIRE(level >= 1 && level <= p->Lc, "stk_mg_set_member_matrices: level %d is not one of 1..%d", level, p->Lc);
     STK_REQUIRE(n_kinds >= 1 && (p->n_kinds == 0 || p->n_kinds == n_kinds),
                 "stk_mg_set_member_matrices: %d matrices, %d at the first call", n_kinds, p->n_kinds);
+    // A refused call leaves the plan as it was: the diagonals are looked for on the host,
+    // before the fill kernel below writes a single entry of the members already in use.
+    for (int k = 0; k < n_kinds; ++k) {
+        if (indptr[k] == nullptr) continue;
+        STK_REQUIRE(indices[k] && data[k], "stk_mg_set_member_matrices: matrix %d lacks its arrays", k);
+        int n_missing = 0;
+        for (int32_t i = 0; i < n; ++i) {
+            const int32_t *b = indices[k] + indptr[k][i], *e = indices[k] + indptr[k][i + 1];
+            const int32_t *at = std::lower_bound(b, e, i);
+            if (at == e || *at != i) ++n_missing;
+        }
+        STK_REQUIRE(n_missing == 0, "stk_mg_set_member_matrices: %d rows of level %d lack their diagonal entry",
+                    n_missing, level);
+    }
     if (p->u_vmem == nullptr) {
         const size_t nv = (size_t)n_kinds * p->u_rows * p->KU, nd = (size_t)n_kinds * p->u_rows;
         STK_HIP(hipMalloc((void **)&p->u_vmem, sizeof(double) * nv));
