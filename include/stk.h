@@ -1349,6 +1349,57 @@ int stk_err_element(void *stream, stk_err_plan *plan, int32_t nq,
                     int64_t stride_lo, const double *u_hi, int64_t stride_hi,
                     double *out4);
 
+/* ---- history maps: peak, dose, rates and threshold times of every row in one scan ----
+ * A row is a function of time that is piecewise linear between the nodes t_k = (double)k h:
+ * a spatial dof of a trial-space slab, or a point the sampler evaluated at the nodes.
+ * stk_history_scan reduces every row along time into a STATE of STK_HISTORY_STATE = 9
+ * doubles, state [9][M] (DEVICE, row-major, in/out):
+ *     0 peak, 1 t_peak, 2 dose, 3 time_above, 4 t_first, 5 t_last, 6 max_rate, 7 min_rate,
+ *     8 last (the value at the last node seen).
+ * u[i*row_stride + c*col_stride] is row i at node k_first + c, c < n_cols.  With fresh != 0
+ * column 0 INITIALISES the state (it is not read):
+ *     peak = last = v,  t_peak = (double)k h,  dose = time_above = 0.0,
+ *     t_first = t_last = (double)k h if v > threshold, else NaN,
+ *     max_rate = -inf,  min_rate = +inf.
+ * Every further column k, with a = last, b = its value, e = k - 1, in this order and every
+ * operation rounded on its own (no fused multiply-adds):
+ *     if b > peak:  peak = b, t_peak = (double)k h        (strict: the earliest node wins a tie)
+ *     dose = dose + (a + b) * (0.5 * h)
+ *     rate = (b - a) / h;  max_rate, min_rate by strict comparisons
+ *     a > threshold and b > threshold:  time_above += h,  t_last = (double)k h
+ *     only b > threshold:  x = (threshold - a) / (b - a),  time_above += h * (1.0 - x),
+ *                          t_first = ((double)e + x) * h if it is still NaN,  t_last = (double)k h
+ *     only a > threshold:  x = (threshold - a) / (b - a),  time_above += h * x,
+ *                          t_last = ((double)e + x) * h
+ *     last = b.
+ * No division happens unless a and b lie on different sides of the threshold.  Because
+ * `last` is carried, a scan of [k0, k1) followed by one of [k1, k2) with fresh = 0 gives the
+ * doubles of one scan of [k0, k2): the result depends neither on how the columns are cut
+ * (ranks, chunks) nor on the launch shape.
+ *
+ * Exactly two layouts are served:
+ *   slab        col_stride == 1, row_stride = ld >= n_cols: time contiguous (a slab of this
+ *               library).  A workgroup streams the run of its rows through LDS and one lane
+ *               walks one row; columns c >= n_cols are never read.  u need only be 8-byte
+ *               aligned (base + 8 skip for a scan that starts at column skip).
+ *   time-major  row_stride == 1, col_stride >= M: the (n_k, n_p) block of stk_sample_eval.
+ *               One lane per row, coalesced loads, no LDS.
+ * All offsets are 64-bit; no atomics; nothing is allocated and nothing synchronises.
+ * n_cols == 0 with fresh == 0 leaves the state untouched.  Refused (non-zero, the text of
+ * stk_last_error names the argument, state untouched): a null u or state, M < 0, n_cols < 0,
+ * fresh with n_cols == 0, k_first < 0, h not finite or <= 0, a NaN threshold (+-inf are
+ * allowed: never / always above), a stride pair that is neither layout.
+ *
+ * stk_history_tile sets the tile of the slab form for the launches that follow, process-wide
+ * (measurement and tests; results never depend on it): `rows` per workgroup -- 64, 128, 256
+ * or 512 -- and the LDS a workgroup may take in KiB, 1..64, which sets the columns per chunk
+ * (at least one); 0 for either = the default.  Anything else is refused. */
+#define STK_HISTORY_STATE 9
+int stk_history_tile(int32_t rows, int32_t lds_kib);
+int stk_history_scan(void *stream, int64_t M, int32_t n_cols, const double *u,
+                     int64_t row_stride, int64_t col_stride, int64_t k_first, double h,
+                     double threshold, int32_t fresh, double *state);
+
 /* ---- plan construction on the host threads: processing order and union pattern ---
  * stk_tile_order: the mesh-tile order of n dofs with coordinates coords [n][d]
  * (d = 2 or 3): the bounding box cut into cubes of edge `side` from the corner `lo`

@@ -165,17 +165,29 @@ class HeatEquation:
         u = self._trial_vector(u)
         return sample_collective(self.sample_plan, u, times, points, field=field)
 
-    def _trial_vector(self, u):
-        """`u` as a device vector, and the sampling plan built on first use."""
+    def _trial_vector(self, u, plan=True):
+        """`u` as a device vector, and (with `plan`) the sampling plan built on first use."""
         from source.linop import _is_device_vector
         from source.sampling import SamplePlan
         if not _is_device_vector(u):
             u = device_vector(u, self.N)
         assert u.N == self.N and u.M == self.M, 'sampling takes vectors of the trial space'
-        if self.sample_plan is None:
+        if plan and self.sample_plan is None:
             mesh_space, mesh_time = self._sample_meshes
             self.sample_plan = SamplePlan(mesh_space, mesh_time)
         return u
+
+    def history_maps(self, u, threshold=None, points=None, fields=None):
+        """The thermal history of a trial-space vector `u` -- flat NumPy vector or device
+        vector -- over [0, T]: the dict of heateq_mpi.py's history_maps() (source/history.py,
+        csrc/history.hip): 'peak', 't_peak', 'dose', 'max_rate', 'min_rate' and, with a
+        `threshold`, 'time_above', 't_first', 't_last'; (M,) device tensors in free-dof order,
+        or (n_p,) tensors plus 'inside' at `points` (n_p, d).  Test-space vectors are refused.
+        Out of scope: time windows other than [0, T], several thresholds in one call, per-row
+        thresholds."""
+        from source.history import check_arguments, history_maps
+        check_arguments(threshold, points, self._sample_meshes[0].points.shape[1], fields)  # before the upload
+        return history_maps(self, self._trial_vector(u, plan=points is not None), threshold, points, fields)
 
     def sample_along(self, u, times, points, fields=('u',)):
         """u_h, its time derivative and its gradient along a trajectory: at the PAIRS
@@ -239,7 +251,7 @@ _OPTIONS = (
     ('J_space', int, 6, 'number of space refines'),
     ('precond', str, 'multigrid', 'spatial preconditioner: multigrid or direct.'),
     ('alpha', float, 0.3, 'Alpha value used in the preconditioner for X.'),
-) + driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS  # taken off the command line before the constructor sees it
+) + driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS + driver.HISTORY_OPTIONS  # taken off the command line before the constructor sees it
 
 
 def main(argv=None):
@@ -248,6 +260,7 @@ def main(argv=None):
         parser.add_argument('--' + flag, type=kind, default=default, help=text)
     args, tracking = driver.take_track_options(parser.parse_args(argv))
     args, sampling = driver.take_sample_options(args)
+    args, history_maps = driver.take_history_options(args)
     print('Arguments: %s' % args)
     print('\n\nCreating HeatEquation with %d time refines and %d space refines.'
           % (args.J_time, args.J_space))
@@ -263,6 +276,8 @@ def main(argv=None):
         driver.write_samples(heat, u, sampling)
     if tracking is not None:
         driver.write_track(heat, u, tracking)
+    if history_maps is not None:
+        driver.write_history(heat, u, history_maps)
     if sampling is not None and sampling.error_norms:
         driver.report_error_norms(heat, u)  # this driver keeps no record: the line is the report
     return heat, u, iters

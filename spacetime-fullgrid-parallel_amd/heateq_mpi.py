@@ -594,6 +594,31 @@ class HeatEquationMPI:
         return plan.adjoint_pairs(self.dofs_distr, weights, times, plan.locate(points), field=field, out=out,
                                   accumulate=accumulate)
 
+    def history_maps(self, u, threshold=None, points=None, fields=None):
+        """The thermal history of a trial-space vector `u` (KronVectorMPI) over [0, T], from one
+        scan along time on the device (source/history.py, csrc/history.hip): a dict of device
+        tensors 'peak' and 't_peak' (the largest nodal value and the earliest node that has
+        it), 'dose' (the integral over time, the trapezoid sum of the piecewise linear
+        function), 'max_rate' and 'min_rate' (the largest and smallest d/dt u_h), and with a
+        `threshold` 'time_above' (how long u_h > threshold), 't_first' and 't_last' (the first
+        time it gets above and the last time it is above; NaN if never).  threshold=None scans
+        with +inf and leaves those three out.  `fields`: a subset of the names to return.
+        Without `points`: (M,) tensors in free-dof order.  With `points` (n_p, d) -- NumPy
+        array, device tensor or what ``sample_plan.locate`` returned --: (n_p,) tensors of u_h
+        there (through ``sample`` at the nodes, in column chunks of at most 256 MB) plus
+        'inside'; NaN in every field at points outside the mesh.  COLLECTIVE and independent of
+        the number of ranks, bit for bit: the scan's state travels down the ranks in time order
+        (size - 1 transfers of 72 M bytes, serial by design).  A wrong shape, an unknown field
+        or a NaN threshold raises ValueError before anything touches the GPU.  Test-space
+        vectors are refused.  Out of scope: time windows other than [0, T], several thresholds
+        in one call, per-row thresholds."""
+        from source.history import check_arguments, history_maps
+        check_arguments(threshold, points, self._sample_meshes[0].points.shape[1], fields)  # before a plan is built
+        assert u.dofs_distr.N == self.N and u.M == self.M, 'history_maps() takes vectors of the trial space'
+        if points is not None:
+            self._sample_plan_for(u)
+        return history_maps(self, u, threshold, points, fields)
+
     def error_norms(self, u, exact=None, exact_grad=None, times=None):
         """|| u - u_h || of a trial-space vector `u` (KronVectorMPI) against `exact`
         (t, x, y[, z]) -- a pointwise function of float64 tensors that broadcast, evaluated on
@@ -633,8 +658,10 @@ def main(argv=None):
                                 'reference\'s arithmetic (r.Pr history within 1e-10 of the CPU '
                                 'path); fast: both regrouped everywhere (4 %% less solve time, history '
                                 'within 4.6e-10); reference: every regrouping of the build off '
-                                '(2.3x slower than fast)')] + list(driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS))
+                                '(2.3x slower than fast)')] + list(driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS
+                                                                      + driver.HISTORY_OPTIONS))
     args, tracking = driver.take_track_options(args)
+    args, history_maps = driver.take_history_options(args)
     args, sampling = driver.take_sample_options(args)
     comm, rank, size = driver.start(args)
     heat = HeatEquationMPI(**driver.solver_arguments(args))
@@ -699,6 +726,8 @@ def main(argv=None):
         driver.write_samples(heat, solution, sampling, rank)  # collective
     if tracking is not None:
         driver.write_track(heat, solution, tracking, rank)  # collective
+    if history_maps is not None:
+        driver.write_history(heat, solution, history_maps, rank)  # collective
     if sampling is not None and sampling.error_norms:
         norms = driver.report_error_norms(heat, solution, rank)  # collective
         if norms is not None:

@@ -277,6 +277,8 @@ _PROTOTYPES = {
     'stk_err_points': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p]),
     'stk_err_element': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p,
                                        c_i64, c_p]),
+    'stk_history_scan': (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_i64, c_i64, c_i64, c_f64, c_f64, c_i32, c_p]),
+    'stk_history_tile': (ctypes.c_int, [c_i32, c_i32]),
     'stk_tile_order': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_f64, c_p]),
     'stk_csr_union_count': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_p]),
     'stk_csr_union_fill': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),

@@ -39,6 +39,13 @@ TRACK_OPTIONS = (
      ' problem (e.g. under the moving source) to this .npz'),
     ('track_points', int, 1025, 'number of equally spaced times from 0 to T along the path'),
 )
+# ... and for the history maps of the solution (peak, dose, rates, threshold times)
+HISTORY_OPTIONS = (
+    ('history_out', str, None, 'write the history maps of the solution (peak, t_peak, dose, max_rate, min_rate; with a'
+     ' threshold also time_above, t_first, t_last) on a raster to this .npz'),
+    ('history_threshold', float, None, 'threshold of the history maps (default: none)'),
+    ('history_raster', int, 129, 'raster points per axis over the bounding box of the mesh'),
+)
 
 
 def device_mb():
@@ -139,6 +146,13 @@ def take_track_options(args):
     return args, (tracking if tracking.track_out else None)
 
 
+def take_history_options(args):
+    """(the parsed command line without the history options, those options or None without
+    --history_out)."""
+    history = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in HISTORY_OPTIONS})
+    return args, (history if history.history_out else None)
+
+
 def report_error_norms(heat, solution, rank=0):
     """--error_norms: one line with the four norms of u - u_h and the relative errors
     (heat.error_norms, collective; works for both solve drivers), and the dict for the
@@ -175,6 +189,20 @@ def write_samples(heat, solution, args, rank=0):
             np.savez(f, times=times, points=points, inside=located.inside.cpu().numpy(),
                      values=values.cpu().numpy())
     return values
+
+
+def write_history(heat, solution, args, rank=0):
+    """--history_out: the history maps of the solution on a raster of history_raster^d points
+    over the bounding box, written by rank 0 as an .npz with points (R^d, d), inside (R^d,) and
+    one (R^d,) array per field (heat.history_maps with points; the three threshold fields only
+    with --history_threshold).  Collective; works for both solve drivers."""
+    from .sampling import raster
+    points = raster(heat._sample_meshes[0], args.history_raster)
+    got = heat.history_maps(solution, threshold=args.history_threshold, points=points)
+    if rank == 0:
+        with open(args.history_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
+            np.savez(f, points=points, **{k: v.cpu().numpy() for k, v in got.items()})
+    return got
 
 
 def require_path(heat, args):
