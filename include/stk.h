@@ -47,8 +47,8 @@ int stk_device_info(int32_t *n_cu, int32_t *wave_size, int64_t *hbm_bytes);
  * created and hold for its lifetime.  "Bit-identical" means results never depend
  * on the key; "rounding" means the last bits may change.
  *   ell_wg_per_cu        (launch, 0..16, default 0) persistent workgroups per CU
- *                        of stk_kron_ell_apply; 0 = 2 for K >= 12, else 3.
- *                        Bit-identical.
+ *                        of stk_kron_ell_apply; 0 = 2 for K >= 12, else 3; never
+ *                        more than fit 160 KiB of LDS.  Bit-identical.
  *   ell_force_wide       (launch, 0..1, default 0) 64-bit addressing in the
  *                        sliced-ELL Kronecker kernels on small slabs (tests).
  *                        Bit-identical.
@@ -58,8 +58,9 @@ int stk_device_info(int32_t *n_cu, int32_t *wave_size, int64_t *hbm_bytes);
  *                        packed form of stk_kron_plan_create.  Bit-identical.
  *   pack_multi_lanes     (launch, 0..2, default 1) stk_kron_pack_apply_multi:
  *                        1 = a lane group per term on long slabs, turns on short
- *                        ones; 2 = lane groups always; 0 = turns always.
- *                        Bit-identical.
+ *                        ones; 2 = lane groups wherever two slot rows fit a
+ *                        workgroup (at most 256 lanes per slot row); 0 = turns
+ *                        always.  Bit-identical.
  *   pack_check_steps     (launch, 0..1, default 0) stk_kron_pack_apply_multi_steps
  *                        checks the stated time steps against the factors (one
  *                        stream synchronisation per call; tests).  No effect on
@@ -421,8 +422,12 @@ int stk_kron_ell_ghost_apply(void *stream, const stk_ell_pattern *pattern_host,
  * ghost time steps interleaved: ghosts[2*j] = x[j, t = -1] (X_loc_bdr[0],
  * mpi_vector.py:148-175), ghosts[2*j + 1] = x[j, t = n_loc] (X_loc_bdr[-1]);
  * a side without a neighbour is zero-filled.  K one of 5, 7, 9, 12, 16; at most
- * 3 terms; slabs of any size (64-bit addressing).  The stores of y and the loads
- * of the slot stream are non-temporal. */
+ * 3 terms; n_loc <= 1020 (one lane per pair of time steps and the ghost lane in a
+ * workgroup of 512), and less where n_terms * rows_per_unit * (n_loc + 3) sums, the
+ * dictionary and the time factors exceed 64 KiB of LDS for a single slot row (the
+ * call is refused: with a dictionary of 16 codes from 1017 steps on for two terms,
+ * 676 for three, and with row pairs 810 and 537); slabs of any size (64-bit
+ * addressing).  The stores of y and the loads of the slot stream are non-temporal. */
 typedef struct {
     int32_t M, K;
     int32_t col_bits; /* 2^col_bits >= M */
@@ -531,8 +536,9 @@ int stk_kron_pack_boundary_apply(void *stream, const stk_pack_pattern *pattern_h
  * factor couples to the neighbour ranks' rows takes stk_kron_pack_apply.  The
  * pattern must have a dictionary; xs_host: n_terms device pointers (host array),
  * 2 or 3 terms.  Every row's sums are those of stk_kron_pack_apply, term by term,
- * bit for bit.  (Slot rows that would need more than 512 lanes, and tuning key
- * "pack_multi_lanes" = 0: the terms take turns in one lane, round 4's form.) */
+ * bit for bit.  (Slot rows that would need more than 256 lanes -- fewer than two
+ * of them per workgroup of 512 -- and tuning key "pack_multi_lanes" = 0: the terms
+ * take turns in one lane, round 4's form.) */
 int stk_kron_pack_apply_multi(void *stream, const stk_pack_pattern *pattern_host,
                               int32_t n_loc, int32_t ld, int32_t n_terms,
                               const stk_kron_pack_term *terms_host,

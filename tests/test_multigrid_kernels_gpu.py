@@ -68,7 +68,9 @@ LD = ref.LD
 GUARD, SENTINEL, BEHIND = 4, 7.25, -3.5  # 4 guard rows; BEHIND fills the columns behind the pair
 NAN = float('nan')
 DEFAULTS = dict(mg_strip_mb=250, mg_strip_width=2, mg_zero_start=1, mg_gs_diag_free=1, mg_fuse_restrict=1,
-                mg_restrict_one_pass=1, mg_fuse_coarse=1, mg_coarse_lds=1, mg_coarse_uniform=1, rows_force_wide=0)
+                mg_restrict_one_pass=1, mg_fuse_coarse=1, mg_coarse_lds=1, mg_coarse_uniform=1, rows_force_wide=0,
+                # (the Kronecker-sum kernels' keys: tests/test_kron_kernels_gpu.py shares `tuning`)
+                ell_wg_per_cu=0, ell_force_wide=0, pack_multi_lanes=1, pack_check_steps=0)
 
 
 @pytest.fixture(scope='module')
