@@ -1406,6 +1406,87 @@ int stk_history_scan(void *stream, int64_t M, int32_t n_cols, const double *u,
                      int64_t row_stride, int64_t col_stride, int64_t k_first, double h,
                      double threshold, int32_t fresh, double *state);
 
+/* ---- time curves: heat content, norms, outflow, peak and hot zone per time node ----------
+ * The reductions over SPACE of a trial-space slab, one number per time node: the complement
+ * of the history maps, from one pass over the cells, without downloading the slab.
+ *
+ * The PLAN is built once per mesh from the HOST arrays of stk_err_plan_create, with its
+ * checks; it stores per cell |T| and grad lambda_a (the expressions given there), a mask of
+ * boundary faces, and owns the workspace of the tile partials (at most 8 MiB, or one column
+ * of partials where that is more): one plan serves one stream at a time.
+ *
+ * stk_curves_boundary_faces (HOST only, touches no GPU, serial): bit a of mask[t] is set iff
+ * the face of cell t opposite its vertex a belongs to no other cell of `cells` [nc][d + 1].
+ * The face keys (the other d vertices, ascending) are sorted with the slot as the last key, a
+ * total order: no hash, nothing that could vary from run to run.
+ *
+ * stk_curves_eval reads slab[i * row_stride + c], c < n_cols, i < M = n_free (the caller
+ * offsets the pointer for a column range; 8-byte alignment is all it needs) and writes the
+ * DEVICE array out[q * ld_out + c], q < stk_curves_rows(d) = 7 + 3 d:
+ *     STK_CURVES_HEAT, _L2, _H1, _OUTFLOW, _MEASURE, _MOMENT + j (j < d), then
+ *     STK_CURVES_PEAK(d), _PEAK_ROW(d) (an exact double), _BOX_LO(d) + j, _BOX_HI(d) + j.
+ * Per cell with vertices a = 0 .. d, U_a its nodal values (0.0 for a boundary vertex, no row
+ * is read), g_a = grad lambda_a, every product, quotient and sum rounded on its own:
+ *     S = ((U_0 + U_1) + U_2) [+ U_3],   Q = ((U_0 U_0 + U_1 U_1) + U_2 U_2) [+ U_3 U_3]
+ *     heat     (|T| S) / (d + 1)
+ *     l2_sq    (|T| (S S + Q)) / ((d + 1)(d + 2))
+ *     G_j = ((U_0 g_0j + U_1 g_1j) + U_2 g_2j) [+ U_3 g_3j]
+ *     h1_sq    |T| ((G_0 G_0 + G_1 G_1) [+ G_2 G_2])
+ *     outflow  (d |T|) F,  F = 0.0, then for a ascending with bit a of the face mask set
+ *              F = F + ((G_0 g_a0 + G_1 g_a1) [+ G_2 g_a2])       (n_a |F_a| = -d |T| g_a)
+ * The zone {u_h > threshold}: vertex a is above iff U_a > threshold, strictly.  The vertices
+ * are put in the order q_0 .. q_d, those above in ascending a and then the others in ascending
+ * a, with values W; n are above.  C_ab = q_a + s (q_b - q_a), s = (W_a - threshold) /
+ * (W_a - W_b), a above and b not, so the denominator is positive.  The pieces:
+ *     d = 2  n = 1: X = (q_0, C_01, C_02): X0 X1 X2;  n = 2: X = (q_0, q_1, C_12, C_02): X0 X1
+ *            X2 and X0 X2 X3
+ *     d = 3  n = 1: X = (q_0, C_01, C_02, C_03): X0 X1 X2 X3;  n = 2: X = (q_0, C_02, C_03, q_1,
+ *            C_12, C_13), n = 3: X = (q_0, q_1, q_2, C_03, C_13, C_23): X0 X1 X2 X3, X1 X2 X3 X4
+ *            and X2 X3 X4 X5
+ *     n = d + 1: the cell with its own |T| and its own vertices in their order; n = 0: nothing.
+ * A piece has the measure m = |det| / d! of its edge vectors X_r - X_first (the expressions of
+ * |T|) and adds m to the measure, from 0.0 in the order above, and (m (sum of its vertices,
+ * from the left)) / (d + 1) to moment j.  Every term is >= 0: no "cell minus corner".  The
+ * box is the min / max over the X of the case; an empty one leaves as NaN.
+ * The peak is the largest u over the slab rows and the lowest row that has it; a NaN value
+ * takes no part, and a column of nothing else gives (-inf, M).
+ * The sums over the mesh have the ONE shape of stk_err_element, fixed by nc: tile i is cells
+ * [256 i, 256 i + 256), its 256 lanes (absent cells: 0.0) are added in the tree x[i] + x[i + s],
+ * s = 128, .., 1, and the tile partials in the same tree with P the power of two at or above
+ * the number of tiles (an absent partner adds nothing).  No atomics.  Column c's numbers
+ * depend neither on the columns that share its call, nor on stk_curves_tile (the columns a
+ * workgroup takes in turn, 1..32, 0 = the default 8), nor on stk_curves_batch (the bytes of
+ * partials per column batch, up to the default 8 MiB, 0 = the default), nor on alignment.
+ * threshold = +inf: never above (measure and moment 0.0, the box NaN); -inf: every vertex
+ * above, boundary vertices included; NaN is refused.  Refused with `out` untouched and the
+ * argument named in stk_last_error: a null pointer, n_cols < 1, M != n_free, row_stride or
+ * ld_out below n_cols, a NaN threshold; stk_curves_tile and stk_curves_batch refuse values
+ * outside their ranges.
+ * Out of scope: time windows other than whole nodes, several thresholds per call,
+ * sub-regions of the mesh, values between nodes, test-space vectors. */
+#define STK_CURVES_HEAT 0
+#define STK_CURVES_L2 1
+#define STK_CURVES_H1 2
+#define STK_CURVES_OUTFLOW 3
+#define STK_CURVES_MEASURE 4
+#define STK_CURVES_MOMENT 5
+#define STK_CURVES_PEAK(d) (5 + (d))
+#define STK_CURVES_PEAK_ROW(d) (6 + (d))
+#define STK_CURVES_BOX_LO(d) (7 + (d))
+#define STK_CURVES_BOX_HI(d) (7 + 2 * (d))
+typedef struct stk_curves_plan stk_curves_plan;
+int stk_curves_rows(int32_t d);
+int stk_curves_boundary_faces(int32_t d, int64_t nc, const int64_t *cells, uint8_t *mask);
+int stk_curves_plan_create(int32_t d, int64_t nv, int64_t nc, const double *points,
+                           const int64_t *cells, int64_t n_free,
+                           const int64_t *free_vertices, stk_curves_plan **out);
+int stk_curves_plan_destroy(stk_curves_plan *plan);
+int stk_curves_eval(void *stream, stk_curves_plan *plan, int64_t M, int32_t n_cols,
+                    const double *slab, int64_t row_stride, double threshold,
+                    int64_t ld_out, double *out);
+int stk_curves_tile(int32_t cols);
+int stk_curves_batch(int64_t bytes);
+
 /* ---- plan construction on the host threads: processing order and union pattern ---
  * stk_tile_order: the mesh-tile order of n dofs with coordinates coords [n][d]
  * (d = 2 or 3): the bounding box cut into cubes of edge `side` from the corner `lo`

@@ -5,6 +5,7 @@
 //
 //  * stk_err_plan_create  uploads the mesh and the vertex -> slab-row map, computes |T| and
 //                         the gradients of the barycentric coordinates per cell
+//                         (p1_geometry_kernel of p1_mesh.h, shared with the time curves)
 //  * stk_err_points       the quadrature points of every cell, [d][nc][nq]: the kernel of
 //                         stk_load_points (p1_mesh.h)
 //  * stk_err_element      f [n_k][nc][nq] (and gf [n_k][d][nc][nq]) at those points for the
@@ -43,33 +44,6 @@ constexpr int BS = 256;
 struct err_times {
     double w_lo[STK_ERR_MAX_K], w_hi[STK_ERR_MAX_K], c[STK_ERR_MAX_K];
 };
-
-// |T| and grad lambda_a per cell (p1_volume, p1_gradients), but grad lambda_0 =
-// -((g_1 + g_2) [+ g_3]), the expression of source/assembly.py:_simplex_geometry: it gives
-// -0.0 where p1_gradients gives +0.0 (g_1 = -g_2), the only doubles in which the two differ
-template <int D>
-__global__ __launch_bounds__(BS) void err_geometry_kernel(int64_t nc, const double *__restrict__ p,
-                                                          const int32_t *__restrict__ cells, double *__restrict__ vol,
-                                                          double *__restrict__ grad)
-{
-    const int64_t stride = (int64_t)gridDim.x * BS;
-    for (int64_t t = (int64_t)blockIdx.x * BS + threadIdx.x; t < nc; t += stride) {
-        const p1_simplex<D> s = p1_simplex_of<D>(p, cells + (D + 1) * t);
-        vol[t] = p1_volume(s);
-        double g[D + 1][D];  // g[a][j]
-        p1_gradients(s, g);
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            double sum = g[1][j] + g[2][j];
-            if constexpr (D == 3) sum = sum + g[3][j];
-            g[0][j] = -sum;
-        }
-#pragma unroll
-        for (int a = 0; a <= D; ++a)
-#pragma unroll
-            for (int j = 0; j < D; ++j) grad[((D + 1) * t + a) * D + j] = g[a][j];
-    }
-}
 
 // pairwise tree over the BS lanes of four columns in LDS; the sums end in red[x * BS]
 __device__ inline void tree4(double *red, int tid)
@@ -244,9 +218,9 @@ extern "C" int stk_err_plan_create(int32_t d, int64_t nv, int64_t nc, const doub
     if (e == hipSuccess) {
         const dim3 grid(stk_flat_grid(nc, BS));
         if (d == 2)
-            hipLaunchKernelGGL(err_geometry_kernel<2>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol, p->grad);
+            hipLaunchKernelGGL(p1_geometry_kernel<2>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol, p->grad);
         else
-            hipLaunchKernelGGL(err_geometry_kernel<3>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol, p->grad);
+            hipLaunchKernelGGL(p1_geometry_kernel<3>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol, p->grad);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();

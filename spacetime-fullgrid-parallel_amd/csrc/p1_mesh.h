@@ -1,12 +1,13 @@
 // The simplicial P1 mesh as the load engine (load_dev.hip), the error norms
-// (err_norms.hip) and the sampler (sample.hip) see it: THE definition of the simplex
-// geometry, of the quadrature points of a cell and of the time bracket of a pair, and the
-// host side of a plan -- the mesh check, the int32 cells, the vertex -> slab-row map and
-// the device arrays.  Everything is file-local: a translation unit that includes this
-// gets its own copy, its kernels in its own code object.
+// (err_norms.hip), the sampler (sample.hip) and the time curves (curves.hip) see it: THE
+// definition of the simplex geometry, of |T| and the gradients per cell, of the quadrature
+// points of a cell and of the time bracket of a pair, and the host side of a plan -- the mesh
+// check, the int32 cells, the vertex -> slab-row map and the device arrays.  Everything is
+// file-local: a translation unit that includes this gets its own copy, its kernels in its
+// own code object.
 //
 // ARITHMETIC: every product and every sum rounded on its own.  Contraction is SWITCHED OFF
-// from here on (the pragma below); the three files that include this are also compiled
+// from here on (the pragma below); the four files that include this are also compiled
 // with -ffp-contract=off (Makefile), and nothing here calls fma.
 #pragma once
 #include <cmath>
@@ -144,6 +145,34 @@ __global__ __launch_bounds__(P1_BS) void p1_points_kernel(int64_t total, int32_t
             for (int a = 1; a <= D; ++a) x = x + l[a] * p[D * (int64_t)c[a] + k];
             out[k * total + idx] = x;
         }
+    }
+}
+
+// ---- |T| and the gradients of every cell (the error norms, the time curves) ----------------
+// |T| and grad lambda_a per cell (p1_volume, p1_gradients), but grad lambda_0 =
+// -((g_1 + g_2) [+ g_3]), the expression of source/assembly.py:_simplex_geometry: it gives
+// -0.0 where p1_gradients gives +0.0 (g_1 = -g_2), the only doubles in which the two differ
+template <int D>
+__global__ __launch_bounds__(P1_BS) void p1_geometry_kernel(int64_t nc, const double *__restrict__ p,
+                                                          const int32_t *__restrict__ cells, double *__restrict__ vol,
+                                                          double *__restrict__ grad)
+{
+    const int64_t stride = (int64_t)gridDim.x * P1_BS;
+    for (int64_t t = (int64_t)blockIdx.x * P1_BS + threadIdx.x; t < nc; t += stride) {
+        const p1_simplex<D> s = p1_simplex_of<D>(p, cells + (D + 1) * t);
+        vol[t] = p1_volume(s);
+        double g[D + 1][D];  // g[a][j]
+        p1_gradients(s, g);
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            double sum = g[1][j] + g[2][j];
+            if constexpr (D == 3) sum = sum + g[3][j];
+            g[0][j] = -sum;
+        }
+#pragma unroll
+        for (int a = 0; a <= D; ++a)
+#pragma unroll
+            for (int j = 0; j < D; ++j) grad[((D + 1) * t + a) * D + j] = g[a][j];
     }
 }
 

@@ -47,6 +47,7 @@ class HeatEquation:
         self._sample_meshes, self.sample_plan = (mesh_space, mesh_time), None
         # ... and error_norms() its plan, with the problem's exact solution if it has one
         self.error_plan, self._exact = None, (data.get('exact'), data.get('exact_grad'))
+        self.curves_plan = None  # built by the first time_curves()
         self.path = data.get('path')  # c(t) of a problem that follows one (--track_out), else None
         A_t, L_t, M_t, G_t, u0_t = time_matrices(mesh_time)
         M_Y, Minv_Y, B1_t, B2_t = time_matrices_test_space(mesh_time)
@@ -189,6 +190,19 @@ class HeatEquation:
         check_arguments(threshold, points, self._sample_meshes[0].points.shape[1], fields)  # before the upload
         return history_maps(self, self._trial_vector(u, plan=points is not None), threshold, points, fields)
 
+    def time_curves(self, u, threshold=None):
+        """What a trial-space vector `u` -- flat NumPy vector or device vector -- does over
+        space at every time node: the dict of heateq_mpi.py's time_curves()
+        (source/time_curves.py, csrc/curves.hip): 'heat', 'l2_sq', 'h1_sq', 'outflow', 'peak',
+        'peak_row', 'peak_point' and, with a `threshold`, 'measure_above', 'moment_above',
+        'centroid_above', 'box_lo', 'box_hi'; device tensors with one entry per node.
+        Test-space vectors are refused.  Out of scope: time windows other than the nodes of
+        [0, T], several thresholds in one call, sub-regions of the domain, values between the
+        nodes."""
+        from source.time_curves import check_arguments, time_curves
+        check_arguments(threshold)  # before the upload
+        return time_curves(self, self._trial_vector(u, plan=False), threshold)
+
     def sample_along(self, u, times, points, fields=('u',)):
         """u_h, its time derivative and its gradient along a trajectory: at the PAIRS
         (times[p], points[p]) of a trial-space vector `u` -- flat NumPy vector or device
@@ -251,7 +265,7 @@ _OPTIONS = (
     ('J_space', int, 6, 'number of space refines'),
     ('precond', str, 'multigrid', 'spatial preconditioner: multigrid or direct.'),
     ('alpha', float, 0.3, 'Alpha value used in the preconditioner for X.'),
-) + driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS + driver.HISTORY_OPTIONS  # taken off the command line before the constructor sees it
+) + driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS + driver.HISTORY_OPTIONS + driver.CURVES_OPTIONS  # taken off the command line before the constructor sees it
 
 
 def main(argv=None):
@@ -261,6 +275,7 @@ def main(argv=None):
     args, tracking = driver.take_track_options(parser.parse_args(argv))
     args, sampling = driver.take_sample_options(args)
     args, history_maps = driver.take_history_options(args)
+    args, curves = driver.take_curves_options(args)
     print('Arguments: %s' % args)
     print('\n\nCreating HeatEquation with %d time refines and %d space refines.'
           % (args.J_time, args.J_space))
@@ -278,6 +293,8 @@ def main(argv=None):
         driver.write_track(heat, u, tracking)
     if history_maps is not None:
         driver.write_history(heat, u, history_maps)
+    if curves is not None:
+        driver.write_curves(heat, u, curves)
     if sampling is not None and sampling.error_norms:
         driver.report_error_norms(heat, u)  # this driver keeps no record: the line is the report
     return heat, u, iters

@@ -247,6 +247,7 @@ class HeatEquationMPI:
         self._sample_meshes, self.sample_plan = (mesh_space, mesh_time), None
         # ... and error_norms() its plan, with the problem's exact solution if it has one
         self.error_plan, self._exact = None, (data.get('exact'), data.get('exact_grad'))
+        self.curves_plan = None  # built by the first time_curves()
         self.path = data.get('path')  # c(t) of a problem that follows one (--track_out), else None
         mark('meshes')
         # the load vector and the prolongations need the mesh only: beside the
@@ -619,6 +620,32 @@ class HeatEquationMPI:
             self._sample_plan_for(u)
         return history_maps(self, u, threshold, points, fields)
 
+    def time_curves(self, u, threshold=None):
+        """What a trial-space vector `u` (KronVectorMPI) does over SPACE at every time node
+        t_k, k = 0 .. N - 1, from one pass over the cells on the device
+        (source/time_curves.py, csrc/curves.hip): a dict of device tensors with one entry per
+        node: 'heat' (the integral of u_h over the domain), 'l2_sq' and 'h1_sq' (the integrals
+        of u_h^2 and |grad u_h|^2), 'outflow' (minus the integral of the normal derivative over
+        the boundary: the heat leaving), 'peak' and 'peak_row' (the largest nodal value over
+        the free dofs and the lowest slab row that has it, int64) and 'peak_point' ((N, d), the
+        coordinates of that row's vertex); and with a `threshold` the zone {u_h > threshold},
+        exact for the P1 function: 'measure_above', 'moment_above' ((N, d), the integral of x
+        over the zone), 'centroid_above' ((N, d), NaN where the measure is 0), 'box_lo' and
+        'box_hi' ((N, d), NaN where the zone is empty).  A vertex AT the threshold is not above,
+        the rule of ``history_maps``; threshold=None leaves the five out.  Boundary vertices
+        carry the value 0.  COLLECTIVE and independent of the number of ranks, bit for bit: a
+        rank evaluates the nodes it owns, the sums over the mesh have one shape fixed by the
+        number of cells, and one all-reduce with one non-zero contributor per entry gives
+        every rank all of it.  A NaN threshold raises ValueError before anything touches the
+        GPU; the plan is built by the first call (``curves_plan``), a run that never asks
+        builds nothing.  Test-space vectors are refused.  Out of scope: time windows other than
+        the nodes of [0, T], several thresholds in one call, sub-regions of the domain, values
+        between the nodes."""
+        from source.time_curves import check_arguments, time_curves
+        check_arguments(threshold)  # before a plan is built
+        assert u.dofs_distr.N == self.N and u.M == self.M, 'time_curves() takes vectors of the trial space'
+        return time_curves(self, u, threshold)
+
     def error_norms(self, u, exact=None, exact_grad=None, times=None):
         """|| u - u_h || of a trial-space vector `u` (KronVectorMPI) against `exact`
         (t, x, y[, z]) -- a pointwise function of float64 tensors that broadcast, evaluated on
@@ -659,9 +686,10 @@ def main(argv=None):
                                 'path); fast: both regrouped everywhere (4 %% less solve time, history '
                                 'within 4.6e-10); reference: every regrouping of the build off '
                                 '(2.3x slower than fast)')] + list(driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS
-                                                                      + driver.HISTORY_OPTIONS))
+                                                                      + driver.HISTORY_OPTIONS + driver.CURVES_OPTIONS))
     args, tracking = driver.take_track_options(args)
     args, history_maps = driver.take_history_options(args)
+    args, curves = driver.take_curves_options(args)
     args, sampling = driver.take_sample_options(args)
     comm, rank, size = driver.start(args)
     heat = HeatEquationMPI(**driver.solver_arguments(args))
@@ -728,6 +756,8 @@ def main(argv=None):
         driver.write_track(heat, solution, tracking, rank)  # collective
     if history_maps is not None:
         driver.write_history(heat, solution, history_maps, rank)  # collective
+    if curves is not None:
+        driver.write_curves(heat, solution, curves, rank)  # collective
     if sampling is not None and sampling.error_norms:
         norms = driver.report_error_norms(heat, solution, rank)  # collective
         if norms is not None:

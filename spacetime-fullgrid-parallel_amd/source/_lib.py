@@ -279,6 +279,13 @@ _PROTOTYPES = {
                                        c_i64, c_p]),
     'stk_history_scan': (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_i64, c_i64, c_i64, c_f64, c_f64, c_i32, c_p]),
     'stk_history_tile': (ctypes.c_int, [c_i32, c_i32]),
+    'stk_curves_rows': (ctypes.c_int, [c_i32]),
+    'stk_curves_boundary_faces': (ctypes.c_int, [c_i32, c_i64, c_p, c_p]),
+    'stk_curves_plan_create': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_i64, c_p, ctypes.POINTER(c_p)]),
+    'stk_curves_plan_destroy': (ctypes.c_int, [c_p]),
+    'stk_curves_eval': (ctypes.c_int, [c_p, c_p, c_i64, c_i32, c_p, c_i64, c_f64, c_i64, c_p]),
+    'stk_curves_tile': (ctypes.c_int, [c_i32]),
+    'stk_curves_batch': (ctypes.c_int, [c_i64]),
     'stk_tile_order': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_f64, c_p]),
     'stk_csr_union_count': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_p]),
     'stk_csr_union_fill': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),

@@ -46,6 +46,13 @@ HISTORY_OPTIONS = (
     ('history_threshold', float, None, 'threshold of the history maps (default: none)'),
     ('history_raster', int, 129, 'raster points per axis over the bounding box of the mesh'),
 )
+# ... and for the time curves of the solution (heat content, norms, outflow, peak, hot zone)
+CURVES_OPTIONS = (
+    ('curves_out', str, None, 'write the time curves of the solution (heat, l2_sq, h1_sq, outflow, peak, peak_row,'
+     ' peak_point per time node; with a threshold also measure_above, moment_above, centroid_above, box_lo, box_hi)'
+     ' to this .npz'),
+    ('curves_threshold', float, None, 'threshold of the hot zone of the time curves (default: none)'),
+)
 
 
 def device_mb():
@@ -153,6 +160,13 @@ def take_history_options(args):
     return args, (history if history.history_out else None)
 
 
+def take_curves_options(args):
+    """(the parsed command line without the curves options, those options or None without
+    --curves_out)."""
+    curves = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in CURVES_OPTIONS})
+    return args, (curves if curves.curves_out else None)
+
+
 def report_error_norms(heat, solution, rank=0):
     """--error_norms: one line with the four norms of u - u_h and the relative errors
     (heat.error_norms, collective; works for both solve drivers), and the dict for the
@@ -202,6 +216,19 @@ def write_history(heat, solution, args, rank=0):
     if rank == 0:
         with open(args.history_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
             np.savez(f, points=points, **{k: v.cpu().numpy() for k, v in got.items()})
+    return got
+
+
+def write_curves(heat, solution, args, rank=0):
+    """--curves_out: the time curves of the solution, written by rank 0 as an .npz with times
+    (N,) and one array per field of heat.time_curves (the five zone fields only with
+    --curves_threshold).  Collective; works for both solve drivers."""
+    got = heat.time_curves(solution, threshold=args.curves_threshold)
+    mesh_time = heat._sample_meshes[1]
+    times = np.array([float(k) * float(mesh_time.h) for k in range(mesh_time.nv)])
+    if rank == 0:
+        with open(args.curves_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
+            np.savez(f, times=times, **{k: v.cpu().numpy() for k, v in got.items()})
     return got
 
 
