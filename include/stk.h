@@ -1487,6 +1487,110 @@ int stk_curves_eval(void *stream, stk_curves_plan *plan, int64_t M, int32_t n_co
 int stk_curves_tile(int32_t cols);
 int stk_curves_batch(int64_t bytes);
 
+/* ---- solidification maps: gradient, cooling rate and front speed per cell ----------------
+ * What happens at the freezing front of a trial-space slab, per CELL: when the mean of the
+ * cell last dropped to or below a threshold, how fast it was cooling and what grad u_h was at
+ * that moment, how often that happened, and the largest |grad u_h|^2 it ever saw.  grad u_h is
+ * constant per cell, so the history maps (rows are dofs or points) cannot see it; mean and
+ * gradient of a cell are linear in time per element, so all of it is ONE scan over the
+ * cells' rows with a carried state, without downloading the slab.
+ *
+ * The PLAN is built once per mesh from the HOST arrays of stk_curves_plan_create, with its
+ * checks; it puts the cells in an order of its own, and stores per cell grad lambda_a (the
+ * doubles of stk_err_plan_create), per tile of 256 consecutive cells of that order the
+ * ascending list of the distinct slab rows its cells touch, and per cell the d + 1 positions
+ * in that list.  A cell's numbers are its own, so the order changes no double; the state is
+ * indexed by the caller's cells.  It owns no workspace: one plan serves any number of streams.
+ *
+ * stk_solid_cell_order (HOST only, touches no GPU, serial): order[i] = the cell in place i
+ * along the Z-curve of the centroids, so that 256 consecutive cells are a compact patch that
+ * shares its rows (in the order meshes come in after refinement, 256 consecutive cells can
+ * share none).  The key of a cell: per axis j the 16 bits trunc((c_j - lo_j) / (hi_j - lo_j) *
+ * 65535), c = ((p_0 + p_1) + p_2 [+ p_3]) / (d + 1) its centroid and [lo, hi] the box of all
+ * points (0 on an axis of no extent), bit b of axis j at bit d b + j; the cells are sorted by
+ * (key, cell): a total order, no hash, the same on every run.  stk_solid_order(1) makes plans
+ * created from then on take the cells as given, stk_solid_order(0) restores the default:
+ * measurement and tests; results never depend on it.
+ *
+ * stk_solid_tile_rows (HOST only, touches no GPU, serial): for tile i = cells [256 i,
+ * 256 i + 256) of `cells` [nc][d + 1], tile_rows[tile_ptr[i] .. tile_ptr[i + 1]) is the
+ * ascending list of the distinct values row_of[v] >= 0 over the vertices v of its cells
+ * (row_of [nv]: the slab row of a vertex, -1 on the boundary), and cell_pos[(d + 1) t + a] the
+ * position of row_of[cells[t][a]] in the list of t's tile, 0xFFFF for a boundary vertex (a
+ * list has at most 256 (d + 1) <= 1024 entries).  tile_ptr has n_tiles + 1 entries, tile_rows
+ * room for (d + 1) nc.  Sort and unique per tile: no hash, nothing that could vary from run
+ * to run.
+ *
+ * stk_solid_scan reads slab[i * row_stride + c], c < n_cols, i < M = n_free, row i at the
+ * node k_first + c (the caller offsets the pointer for a column range; 8-byte alignment is
+ * all it needs), and updates the DEVICE array state[q * nc + t], q < STK_SOLID_ROWS(d) =
+ * 6 + 2 d, row-major, in/out:
+ *     STK_SOLID_T_SOLID, _COOLING_RATE, _N_SOLID, _MAX_GRAD_SQ, _T_MAX_GRAD, _LAST_MEAN,
+ *     STK_SOLID_GRAD_SOLID + j, STK_SOLID_LAST_GRAD(d) + j  (j < d).
+ * Cell t has vertices a = 0 .. d, g_a = grad lambda_a, U_a(k) the slab value of vertex a at
+ * node k and 0.0 for a boundary vertex (no row is read); every product, quotient and sum is
+ * rounded on its own, no fused multiply-add:
+ *     m   = (((U_0 + U_1) + U_2) [+ U_3]) / (double)(d + 1)              the cell mean
+ *     G_j = ((U_0 g_0j + U_1 g_1j) + U_2 g_2j) [+ U_3 g_3j]              j < d
+ *     Q   = (G_0 G_0 + G_1 G_1) [+ G_2 G_2]
+ * With fresh != 0 the first column k initialises the state: t_solid = cooling_rate =
+ * grad_solid[j] = NaN, n_solid = 0.0, max_grad_sq = Q, t_max_grad = (double)k h, last_mean = m,
+ * last_grad = G.  Every further column k, with e = k - 1, a = last_mean, b = m, in this order:
+ *     if Q > max_grad_sq:  max_grad_sq = Q, t_max_grad = (double)k h     (strict: the earliest
+ *                                                                          node wins)
+ *     if a > threshold and b <= threshold:          (the rule of the history maps: AT the
+ *                                                    threshold is not above)
+ *         x = (threshold - a) / (b - a)
+ *         t_solid       = ((double)e + x) * h
+ *         cooling_rate  = (a - b) / h
+ *         grad_solid[j] = last_grad[j] + x * (G_j - last_grad[j])
+ *         n_solid       = n_solid + 1.0
+ *     last_mean = b, last_grad = G
+ * No division happens without a crossing.  NaN data makes no crossing (both comparisons are
+ * false) and a NaN Q never replaces max_grad_sq.  threshold = +-inf is allowed, NaN refused.
+ * |grad u_h|^2 is a convex quadratic in t on every time element, so its maximum over [0, T]
+ * sits at a node: max_grad_sq is the EXACT maximum, not a nodal approximation.
+ * last_mean and last_grad are carried: a scan of [k0, k1) followed by one of [k1, k2) with
+ * fresh = 0 gives the doubles of one scan of [k0, k2).  The result depends neither on ranks,
+ * nor on column chunks, nor on the launch shape (stk_solid_tile), nor on the alignment of the
+ * slab.  The square root of Q and the front speed cooling_rate / |grad_solid| are NOT taken
+ * here: the table is a matter of + - * / only, as every bit-for-bit contract of this library.
+ * Refused with the state untouched and the argument named in stk_last_error: a null pointer,
+ * M != n_free, n_cols < 0, fresh with n_cols == 0, k_first < 0, h not finite or <= 0, a NaN
+ * threshold, row_stride < n_cols.  n_cols == 0 with fresh == 0 leaves the state untouched.
+ * No atomics, nothing allocated per call, nothing synchronises.
+ * stk_solid_tile(cols, lds_kib): measurement and tests; results never depend on it.  cols =
+ * the columns of a chunk (1..128, fewer where the image of the longest tile list would exceed
+ * 64 KiB; 0 = from the budget), lds_kib = the LDS budget of a workgroup (1..64, 0 = the
+ * default 16; a chunk is at least one column whatever the budget).  Values outside are refused.
+ * Out of scope: per-cell thresholds, several thresholds per call, upward crossings, time
+ * windows other than whole nodes, a parallel merge of per-rank states, test-space vectors. */
+#define STK_SOLID_ROWS(d) (6 + 2 * (d))
+#define STK_SOLID_T_SOLID 0
+#define STK_SOLID_COOLING_RATE 1
+#define STK_SOLID_N_SOLID 2
+#define STK_SOLID_MAX_GRAD_SQ 3
+#define STK_SOLID_T_MAX_GRAD 4
+#define STK_SOLID_LAST_MEAN 5
+#define STK_SOLID_GRAD_SOLID 6
+#define STK_SOLID_LAST_GRAD(d) (6 + (d))
+typedef struct stk_solid_plan stk_solid_plan;
+int stk_solid_rows(int32_t d);
+int stk_solid_cell_order(int32_t d, int64_t nv, int64_t nc, const double *points,
+                         const int64_t *cells, int32_t *order);
+int stk_solid_order(int32_t caller_order);
+int stk_solid_tile_rows(int32_t d, int64_t nv, int64_t nc, const int64_t *cells,
+                        const int32_t *row_of, int32_t *tile_ptr, int32_t *tile_rows,
+                        uint16_t *cell_pos);
+int stk_solid_plan_create(int32_t d, int64_t nv, int64_t nc, const double *points,
+                          const int64_t *cells, int64_t n_free,
+                          const int64_t *free_vertices, stk_solid_plan **out);
+int stk_solid_plan_destroy(stk_solid_plan *plan);
+int stk_solid_scan(void *stream, stk_solid_plan *plan, int64_t M, int32_t n_cols,
+                   const double *slab, int64_t row_stride, int64_t k_first, double h,
+                   double threshold, int32_t fresh, double *state);
+int stk_solid_tile(int32_t cols, int32_t lds_kib);
+
 /* ---- plan construction on the host threads: processing order and union pattern ---
  * stk_tile_order: the mesh-tile order of n dofs with coordinates coords [n][d]
  * (d = 2 or 3): the bounding box cut into cubes of edge `side` from the corner `lo`

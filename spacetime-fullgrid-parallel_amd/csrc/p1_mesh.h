@@ -1,5 +1,6 @@
 // The simplicial P1 mesh as the load engine (load_dev.hip), the error norms
-// (err_norms.hip), the sampler (sample.hip) and the time curves (curves.hip) see it: THE
+// (err_norms.hip), the sampler (sample.hip), the time curves (curves.hip) and the
+// solidification scan (solid.hip) see it: THE
 // definition of the simplex geometry, of |T| and the gradients per cell, of the quadrature
 // points of a cell and of the time bracket of a pair, and the host side of a plan -- the mesh
 // check, the int32 cells, the vertex -> slab-row map and the device arrays.  Everything is
@@ -7,7 +8,7 @@
 // own code object.
 //
 // ARITHMETIC: every product and every sum rounded on its own.  Contraction is SWITCHED OFF
-// from here on (the pragma below); the four files that include this are also compiled
+// from here on (the pragma below); the files that include this are also compiled
 // with -ffp-contract=off (Makefile), and nothing here calls fma.
 #pragma once
 #include <cmath>

@@ -48,6 +48,7 @@ class HeatEquation:
         # ... and error_norms() its plan, with the problem's exact solution if it has one
         self.error_plan, self._exact = None, (data.get('exact'), data.get('exact_grad'))
         self.curves_plan = None  # built by the first time_curves()
+        self.solid_plan = None  # built by the first solidification_maps()
         self.path = data.get('path')  # c(t) of a problem that follows one (--track_out), else None
         A_t, L_t, M_t, G_t, u0_t = time_matrices(mesh_time)
         M_Y, Minv_Y, B1_t, B2_t = time_matrices_test_space(mesh_time)
@@ -203,6 +204,18 @@ class HeatEquation:
         check_arguments(threshold)  # before the upload
         return time_curves(self, self._trial_vector(u, plan=False), threshold)
 
+    def solidification_maps(self, u, threshold, points=None, fields=None):
+        """What a trial-space vector `u` -- flat NumPy vector or device vector -- does at the
+        freezing front, per cell: the dict of heateq_mpi.py's solidification_maps()
+        (source/solidification.py, csrc/solid.hip): 't_solid', 'cooling_rate', 'grad_solid',
+        'G', 'front_speed', 'n_solid', 'max_grad', 't_max_grad'; device tensors per cell in the
+        mesh's cell order, or per point plus 'inside' at `points` (n_p, d).  The threshold is
+        required.  Test-space vectors are refused.  Out of scope: per-cell thresholds, several
+        thresholds in one call, melting crossings, time windows other than [0, T]."""
+        from source.solidification import check_arguments, solidification_maps
+        check_arguments(threshold, points, self._sample_meshes[0].points.shape[1], fields)  # before the upload
+        return solidification_maps(self, self._trial_vector(u, plan=points is not None), threshold, points, fields)
+
     def sample_along(self, u, times, points, fields=('u',)):
         """u_h, its time derivative and its gradient along a trajectory: at the PAIRS
         (times[p], points[p]) of a trial-space vector `u` -- flat NumPy vector or device
@@ -265,7 +278,7 @@ _OPTIONS = (
     ('J_space', int, 6, 'number of space refines'),
     ('precond', str, 'multigrid', 'spatial preconditioner: multigrid or direct.'),
     ('alpha', float, 0.3, 'Alpha value used in the preconditioner for X.'),
-) + driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS + driver.HISTORY_OPTIONS + driver.CURVES_OPTIONS  # taken off the command line before the constructor sees it
+) + driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS + driver.HISTORY_OPTIONS + driver.CURVES_OPTIONS + driver.SOLID_OPTIONS  # taken off the command line before the constructor sees it
 
 
 def main(argv=None):
@@ -276,6 +289,7 @@ def main(argv=None):
     args, sampling = driver.take_sample_options(args)
     args, history_maps = driver.take_history_options(args)
     args, curves = driver.take_curves_options(args)
+    args, solid = driver.take_solid_options(args)
     print('Arguments: %s' % args)
     print('\n\nCreating HeatEquation with %d time refines and %d space refines.'
           % (args.J_time, args.J_space))
@@ -295,6 +309,8 @@ def main(argv=None):
         driver.write_history(heat, u, history_maps)
     if curves is not None:
         driver.write_curves(heat, u, curves)
+    if solid is not None:
+        driver.write_solid(heat, u, solid)
     if sampling is not None and sampling.error_norms:
         driver.report_error_norms(heat, u)  # this driver keeps no record: the line is the report
     return heat, u, iters

@@ -248,6 +248,7 @@ class HeatEquationMPI:
         # ... and error_norms() its plan, with the problem's exact solution if it has one
         self.error_plan, self._exact = None, (data.get('exact'), data.get('exact_grad'))
         self.curves_plan = None  # built by the first time_curves()
+        self.solid_plan = None  # built by the first solidification_maps()
         self.path = data.get('path')  # c(t) of a problem that follows one (--track_out), else None
         mark('meshes')
         # the load vector and the prolongations need the mesh only: beside the
@@ -646,6 +647,34 @@ class HeatEquationMPI:
         assert u.dofs_distr.N == self.N and u.M == self.M, 'time_curves() takes vectors of the trial space'
         return time_curves(self, u, threshold)
 
+    def solidification_maps(self, u, threshold, points=None, fields=None):
+        """What a trial-space vector `u` (KronVectorMPI) does at the freezing front, per CELL of
+        the mesh in the mesh's cell order, from one scan over the cells' rows on the device
+        (source/solidification.py, csrc/solid.hip): a dict of device tensors 't_solid' and
+        'cooling_rate' ((nc,): the last time the cell's mean dropped from above `threshold` to
+        it or below, and -d/dt of the mean there; NaN if never), 'grad_solid' ((nc, d): grad
+        u_h at that time), 'G' (its length, the square root taken in torch), 'front_speed'
+        (cooling_rate / G: whatever IEEE gives where G == 0), 'n_solid' (int64: the number of
+        such crossings, re-melts + 1), 'max_grad' and 't_max_grad' (the largest |grad u_h| over
+        [0, T] -- exact, |grad u_h|^2 being a convex quadratic in t per element -- and the
+        earliest node that has it).  A mean AT the threshold is not above, the rule of
+        ``history_maps``.  `fields`: a subset of the names.  With `points` (n_p, d) -- NumPy
+        array, device tensor or what ``sample_plan.locate`` returned --: the fields of the
+        cell that holds each point plus 'inside'; NaN, and -1 for 'n_solid', outside the mesh
+        (a gather by cell; no second scan).  COLLECTIVE and independent of the number of ranks,
+        bit for bit: the scan's state travels down the ranks in time order (size - 1 transfers
+        of 8 (6 + 2 d) nc bytes, serial by design).  A missing or NaN threshold, a wrong shape
+        or an unknown field raises ValueError before anything touches the GPU; the plan is
+        built by the first call (``solid_plan``).  Test-space vectors are refused.  Out of
+        scope: per-cell thresholds, several thresholds in one call, melting crossings, time
+        windows other than [0, T], a parallel merge of per-rank states."""
+        from source.solidification import check_arguments, solidification_maps
+        check_arguments(threshold, points, self._sample_meshes[0].points.shape[1], fields)  # before a plan is built
+        assert u.dofs_distr.N == self.N and u.M == self.M, 'solidification_maps() takes vectors of the trial space'
+        if points is not None:
+            self._sample_plan_for(u)
+        return solidification_maps(self, u, threshold, points, fields)
+
     def error_norms(self, u, exact=None, exact_grad=None, times=None):
         """|| u - u_h || of a trial-space vector `u` (KronVectorMPI) against `exact`
         (t, x, y[, z]) -- a pointwise function of float64 tensors that broadcast, evaluated on
@@ -686,10 +715,12 @@ def main(argv=None):
                                 'path); fast: both regrouped everywhere (4 %% less solve time, history '
                                 'within 4.6e-10); reference: every regrouping of the build off '
                                 '(2.3x slower than fast)')] + list(driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS
-                                                                      + driver.HISTORY_OPTIONS + driver.CURVES_OPTIONS))
+                                                                      + driver.HISTORY_OPTIONS + driver.CURVES_OPTIONS
+                                                                      + driver.SOLID_OPTIONS))
     args, tracking = driver.take_track_options(args)
     args, history_maps = driver.take_history_options(args)
     args, curves = driver.take_curves_options(args)
+    args, solid = driver.take_solid_options(args)
     args, sampling = driver.take_sample_options(args)
     comm, rank, size = driver.start(args)
     heat = HeatEquationMPI(**driver.solver_arguments(args))
@@ -758,6 +789,8 @@ def main(argv=None):
         driver.write_history(heat, solution, history_maps, rank)  # collective
     if curves is not None:
         driver.write_curves(heat, solution, curves, rank)  # collective
+    if solid is not None:
+        driver.write_solid(heat, solution, solid, rank)  # collective
     if sampling is not None and sampling.error_norms:
         norms = driver.report_error_norms(heat, solution, rank)  # collective
         if norms is not None:

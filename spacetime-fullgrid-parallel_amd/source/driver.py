@@ -53,6 +53,12 @@ CURVES_OPTIONS = (
      ' to this .npz'),
     ('curves_threshold', float, None, 'threshold of the hot zone of the time curves (default: none)'),
 )
+# ... and for the solidification maps of the solution (front time, cooling rate, gradient, front speed per cell)
+SOLID_OPTIONS = (
+    ('solid_out', str, None, 'write the solidification maps of the solution (t_solid, cooling_rate, grad_solid, G,'
+     ' front_speed, n_solid, max_grad, t_max_grad per cell, with the centroids) to this .npz; needs --solid_threshold'),
+    ('solid_threshold', float, None, 'threshold whose last downward crossing by a cell\'s mean is its solidification'),
+)
 
 
 def device_mb():
@@ -167,6 +173,16 @@ def take_curves_options(args):
     return args, (curves if curves.curves_out else None)
 
 
+def take_solid_options(args):
+    """(the parsed command line without the solidification options, those options or None
+    without --solid_out).  --solid_out without --solid_threshold ends the run as an argument
+    error does, before anything is built."""
+    solid = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in SOLID_OPTIONS})
+    if solid.solid_out and solid.solid_threshold is None:
+        raise SystemExit('--solid_out needs --solid_threshold: the maps are those of one threshold')
+    return args, (solid if solid.solid_out else None)
+
+
 def report_error_norms(heat, solution, rank=0):
     """--error_norms: one line with the four norms of u - u_h and the relative errors
     (heat.error_norms, collective; works for both solve drivers), and the dict for the
@@ -229,6 +245,21 @@ def write_curves(heat, solution, args, rank=0):
     if rank == 0:
         with open(args.curves_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
             np.savez(f, times=times, **{k: v.cpu().numpy() for k, v in got.items()})
+    return got
+
+
+def write_solid(heat, solution, args, rank=0):
+    """--solid_out: the solidification maps of the solution, written by rank 0 as an .npz with
+    centroids (nc, d) -- the mean of a cell's vertices, in the mesh's cell order --, threshold
+    and one array per field of heat.solidification_maps.  Collective; works for both solve
+    drivers."""
+    got = heat.solidification_maps(solution, threshold=args.solid_threshold)
+    mesh = heat._sample_meshes[0]
+    centroids = np.asarray(mesh.points, dtype=np.float64)[np.asarray(mesh.cells, dtype=np.int64)].mean(axis=1)
+    if rank == 0:
+        with open(args.solid_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
+            np.savez(f, centroids=centroids, threshold=float(args.solid_threshold),
+                     **{k: v.cpu().numpy() for k, v in got.items()})
     return got
 
 

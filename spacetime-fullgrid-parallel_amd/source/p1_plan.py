@@ -1,7 +1,7 @@
 """What the device engines on a P1 mesh share on the Python side (csrc/p1_mesh.h is the C
 side): the mesh as libstk takes it, and the lifetime of a plan.  SamplePlan (sampling.py),
-ErrorPlan (error_norms.py), CurvesPlan (time_curves.py) and DeviceLoadPlan (assembly.py) each
-hold one MeshPlanHandle."""
+ErrorPlan (error_norms.py), CurvesPlan (time_curves.py), SolidPlan (solidification.py) and
+DeviceLoadPlan (assembly.py) each hold one MeshPlanHandle."""
 import ctypes
 
 import numpy as np
