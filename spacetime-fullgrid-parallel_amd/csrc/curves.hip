@@ -431,9 +431,7 @@ void release(stk_curves_plan *p)
 {
     if (!p) return;
     p1_mesh_free(&p->mesh);
-    void *arrays[] = {p->vol, p->grad, p->faces, p->work};
-    for (void *a : arrays)
-        if (a) (void)hipFree(a);
+    p1_free({p->vol, p->grad, p->faces, p->work});
     delete p;
 }
 
@@ -494,15 +492,11 @@ extern "C" int stk_curves_boundary_faces(int32_t d, int64_t nc, const int64_t *c
 extern "C" int stk_curves_plan_create(int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells,
                                       int64_t n_free, const int64_t *free_vertices, stk_curves_plan **out)
 {
-    STK_REQUIRE((d == 2 || d == 3) && nv > 0 && nc > 0 && points && cells && n_free > 0 && free_vertices && out,
-                "stk_curves_plan_create: bad arguments");
-    STK_REQUIRE(n_free < ((int64_t)1 << 31), "stk_curves_plan_create: mesh too large for 32-bit tables");
-    if (int rc = p1_check_mesh("stk_curves_plan_create", d, nv, nc, points, cells)) return rc;
+    const char *who = "stk_curves_plan_create";
     std::vector<int32_t> row_of;
-    if (int rc = p1_row_of("stk_curves_plan_create", nv, n_free, free_vertices, &row_of)) return rc;
+    if (int rc = p1_plan_open(who, d, nv, nc, points, cells, n_free, free_vertices, out, &row_of)) return rc;
     std::vector<uint8_t> faces((size_t)nc);
     if (int rc = stk_curves_boundary_faces(d, nc, cells, faces.data())) return rc;
-    const int64_t ns = (int64_t)(d + 1) * nc;
 
     stk_curves_plan *p = new stk_curves_plan();
     p->d = d, p->nv = nv, p->nc = nc, p->n_free = n_free;
@@ -511,32 +505,13 @@ extern "C" int stk_curves_plan_create(int32_t d, int64_t nv, int64_t nc, const d
     p->n_work = p->n_tiles > row_tiles ? p->n_tiles : row_tiles;  // (below 2^23 by the checks above: one grid takes it)
     const int64_t one_column = (int64_t)n_rows(d) * p->n_work;
     p->work_doubles = std::max(one_column, BATCH_BYTES / 8);
-    if (int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, cells, &row_of)) {
+    int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, cells, &row_of);
+    if (!rc) rc = p1_upload(&p->faces, faces.data(), faces.size());
+    if (!rc) rc = p1_geometry(who, p, &p->vol);
+    if (!rc) rc = p1_hip(who, hipMalloc((void **)&p->work, (size_t)p->work_doubles * sizeof(double)));
+    if (rc) {
         release(p);
         return rc;
-    }
-    if (int rc = p1_upload(&p->faces, faces.data(), faces.size())) {
-        release(p);
-        return rc;
-    }
-    hipError_t e = hipMalloc((void **)&p->vol, (size_t)nc * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->grad, (size_t)ns * d * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->work, (size_t)p->work_doubles * sizeof(double));
-    if (e == hipSuccess) {
-        const dim3 grid(stk_flat_grid(nc, P1_BS));
-        if (d == 2)
-            hipLaunchKernelGGL(p1_geometry_kernel<2>, grid, dim3(P1_BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol,
-                               p->grad);
-        else
-            hipLaunchKernelGGL(p1_geometry_kernel<3>, grid, dim3(P1_BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol,
-                               p->grad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        stk_set_error("stk_curves_plan_create: %s", hipGetErrorString(e));
-        release(p);
-        return 1;
     }
     *out = p;
     return 0;

@@ -187,9 +187,7 @@ void release(stk_err_plan *p)
 {
     if (!p) return;
     p1_mesh_free(&p->mesh);
-    void *arrays[] = {p->vol, p->grad, p->work};
-    for (void *a : arrays)
-        if (a) (void)hipFree(a);
+    p1_free({p->vol, p->grad, p->work});
     delete p;
 }
 
@@ -198,36 +196,18 @@ void release(stk_err_plan *p)
 extern "C" int stk_err_plan_create(int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells,
                                    int64_t n_free, const int64_t *free_vertices, stk_err_plan **out)
 {
-    STK_REQUIRE((d == 2 || d == 3) && nv > 0 && nc > 0 && points && cells && n_free > 0 && free_vertices && out,
-                "stk_err_plan_create: bad arguments");
-    STK_REQUIRE(n_free < ((int64_t)1 << 31), "stk_err_plan_create: mesh too large for 32-bit tables");
-    if (int rc = p1_check_mesh("stk_err_plan_create", d, nv, nc, points, cells)) return rc;
+    const char *who = "stk_err_plan_create";
     std::vector<int32_t> row_of;
-    if (int rc = p1_row_of("stk_err_plan_create", nv, n_free, free_vertices, &row_of)) return rc;
-    const int64_t ns = (int64_t)(d + 1) * nc;
+    if (int rc = p1_plan_open(who, d, nv, nc, points, cells, n_free, free_vertices, out, &row_of)) return rc;
 
     stk_err_plan *p = new stk_err_plan();
     p->d = d, p->nv = nv, p->nc = nc, p->n_free = n_free, p->n_tiles = (nc + BS - 1) / BS;
-    if (int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, cells, &row_of)) {
+    int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, cells, &row_of);
+    if (!rc) rc = p1_geometry(who, p, &p->vol);
+    if (!rc) rc = p1_hip(who, hipMalloc((void **)&p->work, (size_t)p->n_tiles * 4 * sizeof(double)));
+    if (rc) {
         release(p);
         return rc;
-    }
-    hipError_t e = hipMalloc((void **)&p->vol, (size_t)nc * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->grad, (size_t)ns * d * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->work, (size_t)p->n_tiles * 4 * sizeof(double));
-    if (e == hipSuccess) {
-        const dim3 grid(stk_flat_grid(nc, BS));
-        if (d == 2)
-            hipLaunchKernelGGL(p1_geometry_kernel<2>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol, p->grad);
-        else
-            hipLaunchKernelGGL(p1_geometry_kernel<3>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol, p->grad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        stk_set_error("stk_err_plan_create: %s", hipGetErrorString(e));
-        release(p);
-        return 1;
     }
     *out = p;
     return 0;

@@ -133,9 +133,7 @@ void release(stk_load_plan *p)
 {
     if (!p) return;
     p1_mesh_free(&p->mesh);
-    void *arrays[] = {p->vol, p->inc_ptr, p->inc_slot, p->order, p->shares};
-    for (void *a : arrays)
-        if (a) (void)hipFree(a);
+    p1_free({p->vol, p->inc_ptr, p->inc_slot, p->order, p->shares});
     delete p;
 }
 

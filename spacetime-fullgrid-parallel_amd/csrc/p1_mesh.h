@@ -2,16 +2,18 @@
 // (err_norms.hip), the sampler (sample.hip), the time curves (curves.hip) and the
 // solidification scan (solid.hip) see it: THE
 // definition of the simplex geometry, of |T| and the gradients per cell, of the quadrature
-// points of a cell and of the time bracket of a pair, and the host side of a plan -- the mesh
-// check, the int32 cells, the vertex -> slab-row map and the device arrays.  Everything is
-// file-local: a translation unit that includes this gets its own copy, its kernels in its
-// own code object.
+// points of a cell and of the time bracket of a pair, and the host side of a plan -- the
+// opening checks (p1_plan_open: the arguments, the mesh, the vertex -> slab-row map), the int32
+// cells and the device arrays (p1_mesh_upload), |T| and the gradients of every cell
+// (p1_geometry) and what frees a plan's arrays (p1_free).  Everything is file-local: a
+// translation unit that includes this gets its own copy, its kernels in its own code object.
 //
 // ARITHMETIC: every product and every sum rounded on its own.  Contraction is SWITCHED OFF
 // from here on (the pragma below); the files that include this are also compiled
 // with -ffp-contract=off (Makefile), and nothing here calls fma.
 #pragma once
 #include <cmath>
+#include <initializer_list>
 #include <vector>
 
 #include "stk_common.h"
@@ -152,7 +154,8 @@ __global__ __launch_bounds__(P1_BS) void p1_points_kernel(int64_t total, int32_t
 // ---- |T| and the gradients of every cell (the error norms, the time curves) ----------------
 // |T| and grad lambda_a per cell (p1_volume, p1_gradients), but grad lambda_0 =
 // -((g_1 + g_2) [+ g_3]), the expression of source/assembly.py:_simplex_geometry: it gives
-// -0.0 where p1_gradients gives +0.0 (g_1 = -g_2), the only doubles in which the two differ
+// -0.0 where p1_gradients gives +0.0 (g_1 = -g_2), the only doubles in which the two differ.
+// A null `vol`: |T| is not stored (the solidification scan has no use for it).
 template <int D>
 __global__ __launch_bounds__(P1_BS) void p1_geometry_kernel(int64_t nc, const double *__restrict__ p,
                                                           const int32_t *__restrict__ cells, double *__restrict__ vol,
@@ -161,7 +164,7 @@ __global__ __launch_bounds__(P1_BS) void p1_geometry_kernel(int64_t nc, const do
     const int64_t stride = (int64_t)gridDim.x * P1_BS;
     for (int64_t t = (int64_t)blockIdx.x * P1_BS + threadIdx.x; t < nc; t += stride) {
         const p1_simplex<D> s = p1_simplex_of<D>(p, cells + (D + 1) * t);
-        vol[t] = p1_volume(s);
+        if (vol) vol[t] = p1_volume(s);
         double g[D + 1][D];  // g[a][j]
         p1_gradients(s, g);
 #pragma unroll
@@ -224,6 +227,32 @@ inline int p1_row_of(const char *who, int64_t nv, int64_t n_free, const int64_t 
     return 0;
 }
 
+// what the plans of the error norms, the time curves and the solidification scan open with:
+// the arguments, the mesh, and row_of from the free vertices -- all before the first HIP call
+inline int p1_plan_open(const char *who, int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells,
+                        int64_t n_free, const int64_t *free_vertices, const void *out, std::vector<int32_t> *row_of)
+{
+    STK_REQUIRE((d == 2 || d == 3) && nv > 0 && nc > 0 && points && cells && n_free > 0 && free_vertices && out,
+                "%s: bad arguments", who);
+    STK_REQUIRE(n_free < ((int64_t)1 << 31), "%s: mesh too large for 32-bit tables", who);
+    if (int rc = p1_check_mesh(who, d, nv, nc, points, cells)) return rc;
+    return p1_row_of(who, nv, n_free, free_vertices, row_of);
+}
+
+// a HIP call of a plan's set-up: "<who>: <what HIP says>" where it fails
+inline int p1_hip(const char *who, hipError_t e)
+{
+    if (e != hipSuccess) stk_set_error("%s: %s", who, hipGetErrorString(e));
+    return e != hipSuccess;
+}
+
+// the device arrays a plan holds, freed where they are set
+inline void p1_free(std::initializer_list<void *> arrays)
+{
+    for (void *a : arrays)
+        if (a) (void)hipFree(a);
+}
+
 template <typename T>
 int p1_upload(T **dst, const T *src, size_t n)
 {
@@ -252,9 +281,31 @@ inline int p1_mesh_upload(p1_mesh_dev *m, int32_t d, int64_t nv, int64_t nc, con
 
 inline void p1_mesh_free(p1_mesh_dev *m)
 {
-    void *arrays[] = {m->points, m->cells, m->row_of};
-    for (void *a : arrays)
-        if (a) (void)hipFree(a);
+    p1_free({m->points, m->cells, m->row_of});
+}
+
+// plan->grad [nc][d + 1][d] and, where the plan wants |T|, *vol [nc] of the plan's uploaded mesh:
+// allocated here, filled by p1_geometry_kernel on the null stream, complete on return.  A
+// template over the plan, so that only a file that calls it carries the kernel.
+template <class Plan>
+int p1_geometry(const char *who, Plan *plan, double **vol)
+{
+    const int32_t d = plan->d;
+    const int64_t nc = plan->nc;
+    const p1_mesh_dev &m = plan->mesh;
+    hipError_t e = vol ? hipMalloc((void **)vol, (size_t)nc * sizeof(double)) : hipSuccess;
+    if (e == hipSuccess) e = hipMalloc((void **)&plan->grad, (size_t)(d + 1) * nc * d * sizeof(double));
+    if (e == hipSuccess) {
+        const dim3 grid(stk_flat_grid(nc, P1_BS));
+        double *v = vol ? *vol : nullptr;
+        if (d == 2)
+            hipLaunchKernelGGL(p1_geometry_kernel<2>, grid, dim3(P1_BS), 0, 0, nc, m.points, m.cells, v, plan->grad);
+        else
+            hipLaunchKernelGGL(p1_geometry_kernel<3>, grid, dim3(P1_BS), 0, 0, nc, m.points, m.cells, v, plan->grad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    return p1_hip(who, e);
 }
 
 // stk_load_points and stk_err_points: q_points [d][nc][nq] on the device.  A template over the

@@ -519,9 +519,7 @@ void release(stk_sample_plan *p)
 {
     if (!p) return;
     p1_mesh_free(&p->mesh);
-    void *arrays[] = {p->bin_ptr, p->bin_cells, p->req_dev};
-    for (void *a : arrays)
-        if (a) (void)hipFree(a);
+    p1_free({p->bin_ptr, p->bin_cells, p->req_dev});
     if (p->req_host) (void)hipHostFree(p->req_host);
     if (p->copied) (void)hipEventDestroy(p->copied);
     delete p;

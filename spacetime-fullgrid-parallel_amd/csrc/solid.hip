@@ -223,9 +223,7 @@ void release(stk_solid_plan *p)
 {
     if (!p) return;
     p1_mesh_free(&p->mesh);
-    void *arrays[] = {p->grad, p->cell_of, p->tile_ptr, p->tile_rows, p->cell_pos};
-    for (void *a : arrays)
-        if (a) (void)hipFree(a);
+    p1_free({p->grad, p->cell_of, p->tile_ptr, p->tile_rows, p->cell_pos});
     delete p;
 }
 
@@ -320,12 +318,9 @@ extern "C" int stk_solid_tile_rows(int32_t d, int64_t nv, int64_t nc, const int6
 extern "C" int stk_solid_plan_create(int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells,
                                      int64_t n_free, const int64_t *free_vertices, stk_solid_plan **out)
 {
-    STK_REQUIRE((d == 2 || d == 3) && nv > 0 && nc > 0 && points && cells && n_free > 0 && free_vertices && out,
-                "stk_solid_plan_create: bad arguments");
-    STK_REQUIRE(n_free < ((int64_t)1 << 31), "stk_solid_plan_create: mesh too large for 32-bit tables");
-    if (int rc = p1_check_mesh("stk_solid_plan_create", d, nv, nc, points, cells)) return rc;
+    const char *who = "stk_solid_plan_create";
     std::vector<int32_t> row_of;
-    if (int rc = p1_row_of("stk_solid_plan_create", nv, n_free, free_vertices, &row_of)) return rc;
+    if (int rc = p1_plan_open(who, d, nv, nc, points, cells, n_free, free_vertices, out, &row_of)) return rc;
     const int64_t ns = (int64_t)(d + 1) * nc, n_tiles = (nc + BS - 1) / BS;
     // the plan's order of the cells and the cells in that order: tiles, geometry and positions
     // are all taken from `placed`
@@ -348,32 +343,15 @@ extern "C" int stk_solid_plan_create(int32_t d, int64_t nv, int64_t nc, const do
     p->d = d, p->nv = nv, p->nc = nc, p->n_free = n_free, p->n_tiles = n_tiles;
     p->longest = 0;
     for (int64_t i = 0; i < n_tiles; ++i) p->longest = std::max(p->longest, tile_ptr[(size_t)i + 1] - tile_ptr[(size_t)i]);
-    double *vol = nullptr;  // the geometry kernel writes |T| too; the scan has no use for it
     int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, placed.data(), nullptr);
     if (!rc) rc = p1_upload(&p->cell_of, order.data(), order.size());
     if (!rc) rc = p1_upload(&p->tile_ptr, tile_ptr.data(), tile_ptr.size());
     if (!rc) rc = p1_upload(&p->tile_rows, tile_rows.data(), (size_t)tile_ptr[(size_t)n_tiles]);
     if (!rc) rc = p1_upload(&p->cell_pos, cell_pos.data(), cell_pos.size());
+    if (!rc) rc = p1_geometry(who, p, nullptr);  // (the scan has no use for |T|)
     if (rc) {
         release(p);
         return rc;
-    }
-    hipError_t e = hipMalloc((void **)&vol, (size_t)nc * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->grad, (size_t)ns * d * sizeof(double));
-    if (e == hipSuccess) {
-        const dim3 grid(stk_flat_grid(nc, P1_BS));
-        if (d == 2)
-            hipLaunchKernelGGL(p1_geometry_kernel<2>, grid, dim3(P1_BS), 0, 0, nc, p->mesh.points, p->mesh.cells, vol, p->grad);
-        else
-            hipLaunchKernelGGL(p1_geometry_kernel<3>, grid, dim3(P1_BS), 0, 0, nc, p->mesh.points, p->mesh.cells, vol, p->grad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (vol) (void)hipFree(vol);
-    if (e != hipSuccess) {
-        stk_set_error("stk_solid_plan_create: %s", hipGetErrorString(e));
-        release(p);
-        return 1;
     }
     *out = p;
     return 0;

@@ -29,13 +29,15 @@ from source.linop import (BlockDiagLinOp, CompositeLinOp,  # noqa: E402
                           DeviceLinearOperator, InvLinOp, KronLinOp,
                           device_vector, host_vector)
 from source.multigrid import MeshHierarchy, MultiGrid  # noqa: E402
+from source.postprocess import PostProcessing  # noqa: E402
 from source.problem import problem_helper  # noqa: E402
 from source.wavelets import WaveletTransformOp  # noqa: E402
 
 
-class HeatEquation:
+class HeatEquation(PostProcessing):
     """Implementation of Andreev's method for tensor-product trial spaces
-    (reference heateq.py:18-107)."""
+    (reference heateq.py:18-107); sampling, maps, curves and error norms of a solution:
+    source/postprocess.py."""
     def __init__(self, J_space=2, J_time=None, problem='square',
                  precond='multigrid', alpha=0.3, smoothsteps=3, vcycles=2):
         if J_time is None:
@@ -43,12 +45,7 @@ class HeatEquation:
         mesh_space, bc, mesh_time, data, fn = problem_helper(problem,
                                                              J_space=J_space,
                                                              J_time=J_time)
-        # what sample() builds its plan from, on first use
-        self._sample_meshes, self.sample_plan = (mesh_space, mesh_time), None
-        # ... and error_norms() its plan, with the problem's exact solution if it has one
-        self.error_plan, self._exact = None, (data.get('exact'), data.get('exact_grad'))
-        self.curves_plan = None  # built by the first time_curves()
-        self.solid_plan = None  # built by the first solidification_maps()
+        self._init_postprocessing(mesh_space, mesh_time, data)
         self.path = data.get('path')  # c(t) of a problem that follows one (--track_out), else None
         A_t, L_t, M_t, G_t, u0_t = time_matrices(mesh_time)
         M_Y, Minv_Y, B1_t, B2_t = time_matrices_test_space(mesh_time)
@@ -154,121 +151,24 @@ class HeatEquation:
         defect = device_vector(self.g_vec, self.N_Y) - self.B @ u
         return residual.dot(self.P @ residual), defect.dot(self.K @ defect)
 
-    def sample(self, u, times, points, field='u'):
-        """u_h(t_k, x_p) of a trial-space vector `u` -- the flat NumPy vector of the
-        serial operators or a device vector (source.linop.device_vector) -- at `times`
-        (n_k,) in [0, T] and `points` (n_p, d): an (n_k, n_p) device tensor, NaN at points
-        outside the mesh.  The plan of heateq_mpi.py's sample() (source/sampling.py,
-        csrc/sample.hip), built by the first call.  Test-space vectors (discontinuous in
-        time) are out of scope; paired lists (t_p, x_p) are served by ``sample_along``.
-        field='dt' / 'grad': the blocks of the time derivative, (n_k, n_p), and of the
-        gradient, (d, n_k, n_p)."""
-        from source.sampling import sample_collective
-        u = self._trial_vector(u)
-        return sample_collective(self.sample_plan, u, times, points, field=field)
-
-    def _trial_vector(self, u, plan=True):
-        """`u` as a device vector, and (with `plan`) the sampling plan built on first use."""
+    def _trial_vector(self, u, who):
+        """`u` -- the flat NumPy vector of the serial operators or a device vector -- as a device
+        vector (the hook of source/postprocess.py)."""
         from source.linop import _is_device_vector
-        from source.sampling import SamplePlan
         if not _is_device_vector(u):
             u = device_vector(u, self.N)
-        assert u.N == self.N and u.M == self.M, 'sampling takes vectors of the trial space'
-        if plan and self.sample_plan is None:
-            mesh_space, mesh_time = self._sample_meshes
-            self.sample_plan = SamplePlan(mesh_space, mesh_time)
+        assert u.N == self.N and u.M == self.M, '%s takes vectors of the trial space' % who
         return u
 
-    def history_maps(self, u, threshold=None, points=None, fields=None):
-        """The thermal history of a trial-space vector `u` -- flat NumPy vector or device
-        vector -- over [0, T]: the dict of heateq_mpi.py's history_maps() (source/history.py,
-        csrc/history.hip): 'peak', 't_peak', 'dose', 'max_rate', 'min_rate' and, with a
-        `threshold`, 'time_above', 't_first', 't_last'; (M,) device tensors in free-dof order,
-        or (n_p,) tensors plus 'inside' at `points` (n_p, d).  Test-space vectors are refused.
-        Out of scope: time windows other than [0, T], several thresholds in one call, per-row
-        thresholds."""
-        from source.history import check_arguments, history_maps
-        check_arguments(threshold, points, self._sample_meshes[0].points.shape[1], fields)  # before the upload
-        return history_maps(self, self._trial_vector(u, plan=points is not None), threshold, points, fields)
-
-    def time_curves(self, u, threshold=None):
-        """What a trial-space vector `u` -- flat NumPy vector or device vector -- does over
-        space at every time node: the dict of heateq_mpi.py's time_curves()
-        (source/time_curves.py, csrc/curves.hip): 'heat', 'l2_sq', 'h1_sq', 'outflow', 'peak',
-        'peak_row', 'peak_point' and, with a `threshold`, 'measure_above', 'moment_above',
-        'centroid_above', 'box_lo', 'box_hi'; device tensors with one entry per node.
-        Test-space vectors are refused.  Out of scope: time windows other than the nodes of
-        [0, T], several thresholds in one call, sub-regions of the domain, values between the
-        nodes."""
-        from source.time_curves import check_arguments, time_curves
-        check_arguments(threshold)  # before the upload
-        return time_curves(self, self._trial_vector(u, plan=False), threshold)
-
-    def solidification_maps(self, u, threshold, points=None, fields=None):
-        """What a trial-space vector `u` -- flat NumPy vector or device vector -- does at the
-        freezing front, per cell: the dict of heateq_mpi.py's solidification_maps()
-        (source/solidification.py, csrc/solid.hip): 't_solid', 'cooling_rate', 'grad_solid',
-        'G', 'front_speed', 'n_solid', 'max_grad', 't_max_grad'; device tensors per cell in the
-        mesh's cell order, or per point plus 'inside' at `points` (n_p, d).  The threshold is
-        required.  Test-space vectors are refused.  Out of scope: per-cell thresholds, several
-        thresholds in one call, melting crossings, time windows other than [0, T]."""
-        from source.solidification import check_arguments, solidification_maps
-        check_arguments(threshold, points, self._sample_meshes[0].points.shape[1], fields)  # before the upload
-        return solidification_maps(self, self._trial_vector(u, plan=points is not None), threshold, points, fields)
-
-    def sample_along(self, u, times, points, fields=('u',)):
-        """u_h, its time derivative and its gradient along a trajectory: at the PAIRS
-        (times[p], points[p]) of a trial-space vector `u` -- flat NumPy vector or device
-        vector.  The dict of heateq_mpi.py's sample_along(): 'u' (n_p,), 'dt' (n_p,),
-        'grad' (d, n_p) -- those named in `fields` -- and 'inside' (n_p,), device tensors, NaN
-        outside the mesh and outside [0, T]."""
-        from source.sampling import sample_pairs_collective
-        u = self._trial_vector(u)
-        return sample_pairs_collective(self.sample_plan, u, times, points, fields)
-
-    def sample_along_adjoint(self, weights, times, points, field='u', out=None, accumulate=False):
-        """The adjoint E^T of ``sample_along``: numbers given at the pairs (times[p],
-        points[p]) as a functional on the trial space (`weights` (n_p,), for field='grad'
-        (d, n_p)).  Returns (vec, used) as heateq_mpi.py's sample_along_adjoint(): a DEVICE
-        vector (source.linop.host_vector copies it out; ``solve(rhs=vec)`` takes it as it is)
-        and a device bool tensor (n_p,), False where a pair is outside the mesh or [0, T] and
-        contributes nothing.  `out`: a flat NumPy vector or a device vector to overwrite or,
-        with accumulate=True, to add to (a NumPy vector is copied to the device, not changed).
-        One rank, so nothing here is collective."""
+    def _adjoint_target(self, out):
+        """One rank, so nothing of ``sample_along_adjoint`` is collective; a NumPy `out` is
+        copied to the device."""
         from source.linop import _is_device_vector, self_distribution
-        from source.sampling import FIELDS, SamplePlan
-        if field not in FIELDS:  # before a plan is built for it
-            raise ValueError('field must be one of %s, not %r' % (FIELDS, field))
         if out is not None and not _is_device_vector(out):
             if np.size(out) != self.N * self.M:
                 raise ValueError('out is no vector of the trial space')
             out = device_vector(out, self.N)
-        if self.sample_plan is None:
-            mesh_space, mesh_time = self._sample_meshes
-            self.sample_plan = SamplePlan(mesh_space, mesh_time)
-        plan = self.sample_plan
-        return plan.adjoint_pairs(self_distribution(self.N, self.M), weights, times, plan.locate(points), field=field,
-                                  out=out, accumulate=accumulate)
-
-    def error_norms(self, u, exact=None, exact_grad=None, times=None):
-        """|| u - u_h || of a trial-space vector `u` -- flat NumPy vector or device vector
-        -- against `exact` (default: the problem's data['exact'] and data['exact_grad']) in
-        L2(I; L2), L2(I; H^1_0) and in L2(Omega) at `times` (default [T]): the dict of
-        heateq_mpi.py's error_norms() (source/error_norms.py, csrc/err_norms.hip); the plan
-        is built by the first call."""
-        from source.error_norms import ErrorPlan, error_norms_collective
-        from source.linop import _is_device_vector
-        if not _is_device_vector(u):
-            u = device_vector(u, self.N)
-        assert u.N == self.N and u.M == self.M, 'error_norms() takes vectors of the trial space'
-        if exact is None:
-            exact, default_grad = self._exact
-            exact_grad = default_grad if exact_grad is None else exact_grad
-        assert exact is not None, 'this problem has no exact solution: pass exact='
-        if self.error_plan is None:
-            mesh_space, mesh_time = self._sample_meshes
-            self.error_plan = ErrorPlan(mesh_space, mesh_time)
-        return error_norms_collective(self.error_plan, u, exact, exact_grad, times)
+        return self_distribution(self.N, self.M), out
 
 
 _OPTIONS = (
@@ -278,41 +178,26 @@ _OPTIONS = (
     ('J_space', int, 6, 'number of space refines'),
     ('precond', str, 'multigrid', 'spatial preconditioner: multigrid or direct.'),
     ('alpha', float, 0.3, 'Alpha value used in the preconditioner for X.'),
-) + driver.SAMPLE_OPTIONS + driver.TRACK_OPTIONS + driver.HISTORY_OPTIONS + driver.CURVES_OPTIONS + driver.SOLID_OPTIONS  # taken off the command line before the constructor sees it
+) + driver.POST_OPTIONS  # taken off the command line before the constructor sees it
 
 
 def main(argv=None):
     parser = argparse.ArgumentParser(description='Solve the heat equation, serial wiring.')
     for flag, kind, default, text in _OPTIONS:
         parser.add_argument('--' + flag, type=kind, default=default, help=text)
-    args, tracking = driver.take_track_options(parser.parse_args(argv))
-    args, sampling = driver.take_sample_options(args)
-    args, history_maps = driver.take_history_options(args)
-    args, curves = driver.take_curves_options(args)
-    args, solid = driver.take_solid_options(args)
+    args, asked = driver.take_post_options(parser.parse_args(argv))
     print('Arguments: %s' % args)
     print('\n\nCreating HeatEquation with %d time refines and %d space refines.'
           % (args.J_time, args.J_space))
     heat = HeatEquation(**vars(args))
-    if tracking is not None:
-        driver.require_path(heat, tracking)
+    if asked['track'] is not None:
+        driver.require_path(heat, asked['track'])
     print('Size of time mesh: %d dofs. Size of space mesh: %d dofs' % (heat.N, heat.M))
     print('Solving: ', end='')
     u, iters = heat.solve(callback=lambda w, residual, k: print('.', end='', flush=True))
     print('Done in %d  PCG steps. X-norm algebraic error: %s. Error in Yprime: %s\n'
           % ((iters,) + heat.errors(u)))
-    if sampling is not None and sampling.sample_out:
-        driver.write_samples(heat, u, sampling)
-    if tracking is not None:
-        driver.write_track(heat, u, tracking)
-    if history_maps is not None:
-        driver.write_history(heat, u, history_maps)
-    if curves is not None:
-        driver.write_curves(heat, u, curves)
-    if solid is not None:
-        driver.write_solid(heat, u, solid)
-    if sampling is not None and sampling.error_norms:
-        driver.report_error_norms(heat, u)  # this driver keeps no record: the line is the report
+    driver.run_post(heat, u, asked)  # this driver keeps no record: the line of the error norms is the report
     return heat, u, iters
 
 

@@ -144,43 +144,45 @@ def time_operator(comm, op, vec, iters):
                     time_total=MPI.Wtime() - began)
 
 
-def take_sample_options(args):
-    """(the parsed command line without the sampling options, those options or None when
-    neither --sample_out nor --error_norms is given): what the drivers print and record
-    stays what it was."""
-    sampling = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in SAMPLE_OPTIONS})
-    return args, (sampling if sampling.sample_out or sampling.error_norms else None)
+def take_options(args, options, wanted):
+    """(the parsed command line without the flags of the table `options`, those options -- or
+    None where none of the flags `wanted` is given): what the drivers print and record stays
+    what it was."""
+    taken = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in options})
+    return args, (taken if any(getattr(taken, flag) for flag in wanted) else None)
 
 
-def take_track_options(args):
-    """(the parsed command line without the tracking options, those options or None
-    without --track_out)."""
-    tracking = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in TRACK_OPTIONS})
-    return args, (tracking if tracking.track_out else None)
+# what a solve driver can do with its solution: (name, options, the flags that ask for it)
+POST_OPTIONS = SAMPLE_OPTIONS + TRACK_OPTIONS + HISTORY_OPTIONS + CURVES_OPTIONS + SOLID_OPTIONS
+_POST = (('sample', SAMPLE_OPTIONS, ('sample_out', 'error_norms')), ('track', TRACK_OPTIONS, ('track_out',)),
+         ('history', HISTORY_OPTIONS, ('history_out',)), ('curves', CURVES_OPTIONS, ('curves_out',)),
+         ('solid', SOLID_OPTIONS, ('solid_out',)))
 
 
-def take_history_options(args):
-    """(the parsed command line without the history options, those options or None without
-    --history_out)."""
-    history = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in HISTORY_OPTIONS})
-    return args, (history if history.history_out else None)
-
-
-def take_curves_options(args):
-    """(the parsed command line without the curves options, those options or None without
-    --curves_out)."""
-    curves = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in CURVES_OPTIONS})
-    return args, (curves if curves.curves_out else None)
-
-
-def take_solid_options(args):
-    """(the parsed command line without the solidification options, those options or None
-    without --solid_out).  --solid_out without --solid_threshold ends the run as an argument
-    error does, before anything is built."""
-    solid = argparse.Namespace(**{flag: vars(args).pop(flag) for flag, _, _, _ in SOLID_OPTIONS})
-    if solid.solid_out and solid.solid_threshold is None:
+def take_post_options(args):
+    """(the parsed command line without POST_OPTIONS -- never constructor arguments --, asked):
+    asked[name] = the options of 'sample', 'track', 'history', 'curves', 'solid', None where
+    the command line does not ask for it.  --solid_out without --solid_threshold ends the run
+    as an argument error does, before anything is built."""
+    asked = {}
+    for name, options, wanted in _POST:
+        args, asked[name] = take_options(args, options, wanted)
+    if asked['solid'] is not None and asked['solid'].solid_threshold is None:
         raise SystemExit('--solid_out needs --solid_threshold: the maps are those of one threshold')
-    return args, (solid if solid.solid_out else None)
+    return args, asked
+
+
+def run_post(heat, solution, asked, rank=0):
+    """After the solve, what `asked` (take_post_options) asks for, in the fixed order sample,
+    track, history, curves, solid, error norms; every step is collective.  Returns the record
+    of the error norms, None where there is none."""
+    for name, write in (('sample', write_samples), ('track', write_track), ('history', write_history),
+                        ('curves', write_curves), ('solid', write_solid)):
+        if asked[name] is not None and getattr(asked[name], name + '_out'):
+            write(heat, solution, asked[name], rank)
+    if asked['sample'] is not None and asked['sample'].error_norms:
+        return report_error_norms(heat, solution, rank)
+    return None
 
 
 def report_error_norms(heat, solution, rank=0):
@@ -203,6 +205,13 @@ def report_error_norms(heat, solution, rank=0):
     return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in n.items()}
 
 
+def _write_npz(path, rank, **arrays):
+    """Rank 0 writes `arrays` -- device tensors copied out, the rest as it is -- to `path`."""
+    if rank == 0:
+        with open(path, 'wb') as f:  # the name as given: np.savez appends .npz to a path
+            np.savez(f, **{k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in arrays.items()})
+
+
 def write_samples(heat, solution, args, rank=0):
     """--sample_out: the solution on a raster of sample_raster^d points over the bounding
     box at sample_times equally spaced times from 0 to T, written by rank 0 as an .npz with
@@ -214,10 +223,7 @@ def write_samples(heat, solution, args, rank=0):
     points = raster(mesh_space, args.sample_raster)
     values = heat.sample(solution, times, points)
     located = heat.sample_plan.locate(points)
-    if rank == 0:
-        with open(args.sample_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
-            np.savez(f, times=times, points=points, inside=located.inside.cpu().numpy(),
-                     values=values.cpu().numpy())
+    _write_npz(args.sample_out, rank, times=times, points=points, inside=located.inside, values=values)
     return values
 
 
@@ -229,9 +235,7 @@ def write_history(heat, solution, args, rank=0):
     from .sampling import raster
     points = raster(heat._sample_meshes[0], args.history_raster)
     got = heat.history_maps(solution, threshold=args.history_threshold, points=points)
-    if rank == 0:
-        with open(args.history_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
-            np.savez(f, points=points, **{k: v.cpu().numpy() for k, v in got.items()})
+    _write_npz(args.history_out, rank, points=points, **got)
     return got
 
 
@@ -242,9 +246,7 @@ def write_curves(heat, solution, args, rank=0):
     got = heat.time_curves(solution, threshold=args.curves_threshold)
     mesh_time = heat._sample_meshes[1]
     times = np.array([float(k) * float(mesh_time.h) for k in range(mesh_time.nv)])
-    if rank == 0:
-        with open(args.curves_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
-            np.savez(f, times=times, **{k: v.cpu().numpy() for k, v in got.items()})
+    _write_npz(args.curves_out, rank, times=times, **got)
     return got
 
 
@@ -256,10 +258,7 @@ def write_solid(heat, solution, args, rank=0):
     got = heat.solidification_maps(solution, threshold=args.solid_threshold)
     mesh = heat._sample_meshes[0]
     centroids = np.asarray(mesh.points, dtype=np.float64)[np.asarray(mesh.cells, dtype=np.int64)].mean(axis=1)
-    if rank == 0:
-        with open(args.solid_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
-            np.savez(f, centroids=centroids, threshold=float(args.solid_threshold),
-                     **{k: v.cpu().numpy() for k, v in got.items()})
+    _write_npz(args.solid_out, rank, centroids=centroids, threshold=float(args.solid_threshold), **got)
     return got
 
 
@@ -283,9 +282,7 @@ def write_track(heat, solution, args, rank=0):
     points = np.ascontiguousarray(np.asarray(heat.path(times), dtype=np.float64))
     assert points.ndim == 2 and points.shape[0] == len(times), points.shape
     got = heat.sample_along(solution, times, points, fields=('u', 'dt', 'grad'))
-    if rank == 0:
-        with open(args.track_out, 'wb') as f:  # the name as given: np.savez appends .npz to a path
-            np.savez(f, times=times, points=points, **{k: got[k].cpu().numpy() for k in ('inside', 'u', 'dt', 'grad')})
+    _write_npz(args.track_out, rank, times=times, points=points, **{k: got[k] for k in ('inside', 'u', 'dt', 'grad')})
     return got
 
 

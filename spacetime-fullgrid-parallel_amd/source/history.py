@@ -21,6 +21,9 @@ import math
 
 import numpy as np
 
+from .p1_plan import (check_points_shape, device_address, field_names, scan_down_the_ranks, threshold_value,
+                      time_step)
+
 FIELDS = ('peak', 't_peak', 'dose', 'time_above', 't_first', 't_last', 'max_rate', 'min_rate')
 STATE_ROWS = FIELDS + ('last',)
 THRESHOLD_FIELDS = ('time_above', 't_first', 't_last')
@@ -31,25 +34,10 @@ def check_arguments(threshold, points=None, d=None, fields=None):
     """(theta, names) of a ``history_maps`` call, or ValueError; touches no GPU.  threshold:
     None (theta = +inf, the threshold fields are left out) or a number, not NaN; points: None
     or (n_p, d); fields: None (all that the threshold allows) or names of FIELDS."""
-    if threshold is None:
-        theta, allowed = math.inf, tuple(f for f in FIELDS if f not in THRESHOLD_FIELDS)
-    else:
-        theta, allowed = float(threshold), FIELDS
-        if math.isnan(theta):
-            raise ValueError('threshold is NaN')
-    if points is not None and d is not None and not hasattr(points, 'n_p'):  # (located points carry no shape)
-        shape = tuple(points.shape) if hasattr(points, 'shape') else np.asarray(points).shape
-        if len(shape) != 2 or shape[1] != d:
-            raise ValueError('points of shape %s; the mesh takes (n_p, %d)' % (shape, d))
-    if fields is None:
-        return theta, allowed
-    names = (fields,) if isinstance(fields, str) else tuple(fields)
-    for f in names:
-        if f not in FIELDS:
-            raise ValueError('fields must name some of %s, not %r' % (FIELDS, f))
-        if f not in allowed:
-            raise ValueError('%r needs a threshold' % f)
-    return theta, names
+    theta = threshold_value(threshold)
+    check_points_shape(points, d)
+    allowed = FIELDS if threshold is not None else tuple(f for f in FIELDS if f not in THRESHOLD_FIELDS)
+    return theta, field_names(fields, FIELDS, allowed)
 
 
 def plan_chunks(n_nodes, n_p, block_bytes=BLOCK_BYTES):
@@ -67,9 +55,8 @@ def history_scan(u, M, n_cols, strides, k_first, h, threshold, state, fresh):
 
     from . import _lib
     assert tuple(state.shape) == (len(STATE_ROWS), M) and state.is_contiguous() and state.dtype == torch.float64
-    u_ptr = _lib.ptr(u) if torch.is_tensor(u) else u
-    _lib.check(_lib.lib().stk_history_scan(_lib.stream(), M, n_cols, u_ptr, strides[0], strides[1], k_first, float(h),
-                                           float(threshold), int(bool(fresh)), _lib.ptr(state)))
+    _lib.check(_lib.lib().stk_history_scan(_lib.stream(), M, n_cols, device_address(u), strides[0], strides[1], k_first,
+                                           float(h), float(threshold), int(bool(fresh)), _lib.ptr(state)))
     return state
 
 
@@ -85,38 +72,19 @@ def maps_from_state(state, names, outside=None):
     return out
 
 
-def _time_step(vec, mesh_time):
-    if mesh_time is None:
-        from .mesh import construct_interval
-        mesh_time = construct_interval(N=vec.N - 1)
-    assert mesh_time.nv == vec.N, (mesh_time.nv, vec.N)
-    return mesh_time
-
-
 def history_maps_collective(vec, theta, mesh_time=None):
     """The (9, M) state of the whole trial-space vector `vec` (KronVectorMPI) on every rank.
-    COLLECTIVE and serial in the ranks by design: rank r > 0 receives the state from rank
-    r - 1, every rank scans its own columns (fresh on the rank that owns node 0), rank
-    r < size - 1 sends it on -- size - 1 transfers of 72 M bytes.  The last rank's state is
-    the result; the others zero theirs and one all-reduce gives it to all (one non-zero
-    contributor per entry, the pattern of KronVectorMPI.dot; NaN and +-inf survive + 0.0).
-    Every row's operations come in one order, so the doubles are the one-rank doubles."""
+    COLLECTIVE and serial in the ranks by design (p1_plan.scan_down_the_ranks): every rank
+    scans its own columns, fresh on the rank that owns node 0, into the state it received --
+    size - 1 transfers of 72 M bytes.  Every row's operations come in one order, so the
+    doubles are the one-rank doubles."""
     import torch
-    h = float(_time_step(vec, mesh_time).h)
-    dd = vec.dofs_distr
-    comm, rank, size = dd.comm, dd.rank, dd.size
+    h = float(time_step(vec, mesh_time).h)
     state = torch.empty((len(STATE_ROWS), vec.M), dtype=torch.float64, device=vec.buf.device)
     if vec.M == 0:
         return state
-    if rank > 0:
-        comm.wait_all(comm.exchange([], [(state, rank - 1)]))
-    history_scan(vec.buf, vec.M, vec.n_loc, (vec.ld, 1), vec.t_begin, h, theta, state, fresh=vec.t_begin == 0)
-    if rank < size - 1:
-        comm.wait_all(comm.exchange([(state, rank + 1)], []))
-        state.zero_()
-    if size > 1:
-        comm.allreduce_tensor_(state)
-    return state
+    return scan_down_the_ranks(vec, state, lambda state: history_scan(
+        vec.buf, vec.M, vec.n_loc, (vec.ld, 1), vec.t_begin, h, theta, state, fresh=vec.t_begin == 0))
 
 
 def history_points_collective(plan, vec, points, theta, block_bytes=BLOCK_BYTES):
@@ -128,7 +96,7 @@ def history_points_collective(plan, vec, points, theta, block_bytes=BLOCK_BYTES)
     import torch
 
     from .sampling import sample_collective, time_weights
-    mesh_time = _time_step(vec, plan.mesh_time)
+    mesh_time = time_step(vec, plan.mesh_time)
     h, N = float(mesh_time.h), vec.N
     located = plan.locate(points)
     n_p = located.n_p

@@ -27,7 +27,8 @@ import math
 
 import numpy as np
 
-from .p1_plan import MeshPlanHandle
+from .p1_plan import (MeshPlanHandle, check_points_shape, device_address, field_names, scan_down_the_ranks,
+                      threshold_value, time_step)
 
 FIELDS = ('t_solid', 'cooling_rate', 'grad_solid', 'G', 'front_speed', 'n_solid', 'max_grad', 't_max_grad')
 TILE_CELLS = 256
@@ -49,25 +50,9 @@ def check_arguments(threshold, points=None, d=None, fields=None):
     """(theta, names) of a ``solidification_maps`` call, or ValueError; touches no GPU.
     threshold: a number, not NaN -- required; points: None or (n_p, d); fields: None (all) or
     names of FIELDS."""
-    if threshold is None:
-        raise ValueError('solidification_maps needs a threshold')
-    try:
-        theta = float(threshold)
-    except (TypeError, ValueError):
-        raise ValueError('threshold must be a number, not %r' % (threshold,))
-    if math.isnan(theta):
-        raise ValueError('threshold is NaN')
-    if points is not None and d is not None and not hasattr(points, 'n_p'):  # (located points carry no shape)
-        shape = tuple(points.shape) if hasattr(points, 'shape') else np.asarray(points).shape
-        if len(shape) != 2 or shape[1] != d:
-            raise ValueError('points of shape %s; the mesh takes (n_p, %d)' % (shape, d))
-    if fields is None:
-        return theta, FIELDS
-    names = (fields,) if isinstance(fields, str) else tuple(fields)
-    for f in names:
-        if f not in FIELDS:
-            raise ValueError('fields must name some of %s, not %r' % (FIELDS, f))
-    return theta, names
+    theta = threshold_value(threshold, needed_by='solidification_maps')
+    check_points_shape(points, d)
+    return theta, field_names(fields, FIELDS)
 
 
 def tile_rows(cells, row_of):
@@ -121,44 +106,25 @@ def solid_scan(plan, slab, M, n_cols, row_stride, k_first, h, theta, state, fres
     import torch
     _lib = plan._lib
     assert tuple(state.shape) == (n_rows(plan.d), plan.nc) and state.is_contiguous() and state.dtype == torch.float64
-    slab_ptr = _lib.ptr(slab) if torch.is_tensor(slab) else slab
-    _lib.check(_lib.lib().stk_solid_scan(_lib.stream(), plan._plan, int(M), int(n_cols), slab_ptr, int(row_stride),
-                                         int(k_first), float(h), float(theta), int(bool(fresh)), _lib.ptr(state)))
+    _lib.check(_lib.lib().stk_solid_scan(_lib.stream(), plan._plan, int(M), int(n_cols), device_address(slab),
+                                         int(row_stride), int(k_first), float(h), float(theta), int(bool(fresh)),
+                                         _lib.ptr(state)))
     return state
-
-
-def _time_step(vec, mesh_time):
-    if mesh_time is None:
-        from .mesh import construct_interval
-        mesh_time = construct_interval(N=vec.N - 1)
-    assert mesh_time.nv == vec.N, (mesh_time.nv, vec.N)
-    return mesh_time
 
 
 def solidification_collective(plan, vec, theta):
     """The (6 + 2 d, nc) state of the whole trial-space vector `vec` (KronVectorMPI) on every
-    rank.  COLLECTIVE and serial in the ranks by design: rank r > 0 receives the state from
-    rank r - 1, every rank scans its own columns (fresh on the rank that owns node 0), rank
-    r < size - 1 sends it on -- size - 1 transfers of 8 (6 + 2 d) nc bytes.  The last rank's
-    state is the result; the others zero theirs and one all-reduce gives it to all (one
-    non-zero contributor per entry, the pattern of history_maps_collective; NaN and +-inf
-    survive + 0.0).  Every cell's operations come in one order, so the doubles are the
-    one-rank doubles.  A parallel merge of per-rank states is out of scope."""
+    rank.  COLLECTIVE and serial in the ranks by design (p1_plan.scan_down_the_ranks): every
+    rank scans its own columns, fresh on the rank that owns node 0, into the state it received
+    -- size - 1 transfers of 8 (6 + 2 d) nc bytes.  Every cell's operations come in one order,
+    so the doubles are the one-rank doubles.  A parallel merge of per-rank states is out of
+    scope."""
     import torch
     assert vec.M == plan.n_free, (vec.M, plan.n_free)
-    h = float(_time_step(vec, plan.mesh_time).h)
-    dd = vec.dofs_distr
-    comm, rank, size = dd.comm, dd.rank, dd.size
+    h = float(time_step(vec, plan.mesh_time).h)
     state = torch.empty((n_rows(plan.d), plan.nc), dtype=torch.float64, device=vec.buf.device)
-    if rank > 0:
-        comm.wait_all(comm.exchange([], [(state, rank - 1)]))
-    solid_scan(plan, vec.buf, vec.M, vec.n_loc, vec.ld, vec.t_begin, h, theta, state, fresh=vec.t_begin == 0)
-    if rank < size - 1:
-        comm.wait_all(comm.exchange([(state, rank + 1)], []))
-        state.zero_()
-    if size > 1:
-        comm.allreduce_tensor_(state)
-    return state
+    return scan_down_the_ranks(vec, state, lambda state: solid_scan(
+        plan, vec.buf, vec.M, vec.n_loc, vec.ld, vec.t_begin, h, theta, state, fresh=vec.t_begin == 0))
 
 
 def maps_from_state(state, d, names=FIELDS):
@@ -212,11 +178,8 @@ def solidification_maps(heat, u, threshold, points=None, fields=None):
     """What both drivers' ``solidification_maps`` do once `u` is a trial-space KronVectorMPI:
     the checks, the plan on first use (``heat.solid_plan``), the collective, the dict -- per
     cell in the mesh's cell order, or per point (then with 'inside')."""
-    mesh_space, mesh_time = heat._sample_meshes
-    theta, names = check_arguments(threshold, points, mesh_space.points.shape[1], fields)
-    if heat.solid_plan is None:
-        heat.solid_plan = SolidPlan(mesh_space, mesh_time)
-    plan = heat.solid_plan
+    theta, names = check_arguments(threshold, points, heat._sample_meshes[0].points.shape[1], fields)
+    plan = heat._lazy_plan('solid_plan', SolidPlan)
     maps = maps_from_state(solidification_collective(plan, u, theta), plan.d, names)
     if points is None:
         return maps

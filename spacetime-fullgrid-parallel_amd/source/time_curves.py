@@ -23,7 +23,7 @@ import math
 
 import numpy as np
 
-from .p1_plan import MeshPlanHandle
+from .p1_plan import MeshPlanHandle, device_address, threshold_value
 
 SUMS = ('heat', 'l2_sq', 'h1_sq', 'outflow')
 ALWAYS = SUMS + ('peak', 'peak_row', 'peak_point')
@@ -45,15 +45,7 @@ def n_rows(d):
 def check_arguments(threshold):
     """(theta, names) of a ``time_curves`` call, or ValueError; touches no GPU.  threshold:
     None (theta = +inf, the threshold fields are left out) or a number, not NaN."""
-    if threshold is None:
-        return math.inf, ALWAYS
-    try:
-        theta = float(threshold)
-    except (TypeError, ValueError):
-        raise ValueError('threshold must be None or a number, not %r' % (threshold,))
-    if math.isnan(theta):
-        raise ValueError('threshold is NaN')
-    return theta, FIELDS
+    return threshold_value(threshold), (ALWAYS if threshold is None else FIELDS)
 
 
 def boundary_faces(cells):
@@ -86,12 +78,9 @@ def curves_eval(plan, slab, M, n_cols, row_stride, theta, out, ld_out):
     """stk_curves_eval: columns [0, n_cols) of `slab` -- a device tensor or a device address,
     rows row_stride doubles apart -- into out[q * ld_out + c], `out` a device tensor or
     address."""
-    import torch
     _lib = plan._lib
-    slab_ptr = _lib.ptr(slab) if torch.is_tensor(slab) else slab
-    out_ptr = _lib.ptr(out) if torch.is_tensor(out) else out
-    _lib.check(_lib.lib().stk_curves_eval(_lib.stream(), plan._plan, int(M), int(n_cols), slab_ptr, int(row_stride),
-                                          float(theta), int(ld_out), out_ptr))
+    _lib.check(_lib.lib().stk_curves_eval(_lib.stream(), plan._plan, int(M), int(n_cols), device_address(slab),
+                                          int(row_stride), float(theta), int(ld_out), device_address(out)))
     return out
 
 
@@ -144,7 +133,5 @@ def time_curves(heat, u, threshold=None):
     """What both drivers' ``time_curves`` do once `u` is a trial-space KronVectorMPI: the
     checks, the plan on first use (``heat.curves_plan``), the collective, the dict."""
     theta, names = check_arguments(threshold)
-    if heat.curves_plan is None:
-        mesh_space, mesh_time = heat._sample_meshes
-        heat.curves_plan = CurvesPlan(mesh_space, mesh_time)
-    return curves_from_rows(heat.curves_plan, time_curves_collective(heat.curves_plan, u, theta), names)
+    plan = heat._lazy_plan('curves_plan', CurvesPlan)
+    return curves_from_rows(plan, time_curves_collective(plan, u, theta), names)

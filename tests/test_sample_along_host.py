@@ -228,10 +228,12 @@ def test_track_options_and_the_file(tmp_path):
     assert [flag for flag, _, _, _ in driver.TRACK_OPTIONS] == ['track_out', 'track_points']
     assert not {f for f, _, _, _ in driver.TRACK_OPTIONS} & {f for f, _, _, _ in driver.SAMPLE_OPTIONS}
     assert dict((f, d) for f, _, d, _ in driver.TRACK_OPTIONS) == {'track_out': None, 'track_points': 1025}
-    args, tracking = driver.take_track_options(argparse.Namespace(J_time=2, track_out=None, track_points=1025))
+    args, tracking = driver.take_options(argparse.Namespace(J_time=2, track_out=None, track_points=1025), driver.TRACK_OPTIONS,
+                                         ('track_out',))
     assert tracking is None and vars(args) == {'J_time': 2}
     out = str(tmp_path / 'track.npz')
-    args, tracking = driver.take_track_options(argparse.Namespace(J_time=2, track_out=out, track_points=7))
+    args, tracking = driver.take_options(argparse.Namespace(J_time=2, track_out=out, track_points=7), driver.TRACK_OPTIONS,
+                                         ('track_out',))
     assert vars(args) == {'J_time': 2} and tracking.track_out == out and tracking.track_points == 7
 
     path = problem_helper('square_moving_source', J_space=1, J_time=1)[3]['path']
