@@ -1487,6 +1487,57 @@ int stk_curves_eval(void *stream, stk_curves_plan *plan, int64_t M, int32_t n_co
 int stk_curves_tile(int32_t cols);
 int stk_curves_batch(int64_t bytes);
 
+/* ---- isotherms: the level-set segments and triangles of every time node ---------------------
+ * The cut of the time curves' zone itself: per column of a trial-space slab the pieces of
+ * {u_h = threshold} -- segments for d = 2, triangles for d = 3 -- exact for the P1 function.
+ * They are the faces of the zone pieces above that lie on the level set and carry the doubles
+ * that enter box_lo and box_hi.  On a stk_curves_plan; the plan's workspace is not used.
+ *
+ * Everything is the time curves' rule, every product, quotient and sum rounded on its own:
+ * U_a (0.0 for a boundary vertex, no row is read), above iff U_a > threshold strictly, the
+ * order q_0 .. q_d with values W, n of them above, C_ab = q_a + s (q_b - q_a), s =
+ * (W_a - threshold) / (W_a - W_b).  The pieces of a cell, in this order:
+ *     d = 2  n = 1: segment (C_01, C_02);  n = 2: segment (C_12, C_02)
+ *     d = 3  n = 1: triangle (C_01, C_02, C_03);  n = 2: triangles (C_02, C_03, C_12), then
+ *            (C_03, C_12, C_13);  n = 3: triangle (C_03, C_13, C_23)
+ *     n = 0 or d + 1: none.
+ * A vertex AT the threshold is not above (a cut on its edge has s == 1.0 and is that vertex); a
+ * NaN value is not above, and coordinates computed from it are whatever IEEE gives; threshold
+ * = +-inf gives no piece at all; a NaN threshold is refused.  The orientation of a piece is
+ * not promised: the record carries the gradient.
+ *
+ * A piece is one RECORD of stk_iso_width(d) = d d + d + 1 doubles: the vertices X[r][j] at
+ * r d + j; G_j = ((U_0 g_0j + U_1 g_1j) + U_2 g_2j) [+ U_3 g_3j] at d d + j, g the plan's
+ * gradients in the cell's own vertex order (the expression of h1_sq); the cell index at
+ * d d + d, an exact double.  The records are ordered by column, then by cell in the mesh's
+ * order, then as in the table.  No square root is taken: lengths and areas are the caller's.
+ *
+ * The result has no fixed length, so there are two calls, and the scan between them is the
+ * caller's.  Tile t is the cells [256 t, 256 t + 256), n_tiles = ceil(nc / 256).
+ * stk_iso_count writes counts[c * n_tiles + t], the pieces of tile t in column c.
+ * stk_iso_fill takes the counts and first[c * n_tiles + t], the index of that tile's first
+ * record (the caller's exclusive prefix of the counts, in whatever table it assembles), and
+ * writes piece i = first[c][t] + (its rank in the tile) to out[i * W ..] iff 0 <= i < n_out;
+ * nothing else of `out` is touched, so tables that do not belong together cannot make it
+ * write out of bounds.  A (column, tile) with counts == 0 is skipped before a slab row is
+ * read; otherwise the lanes' counts are recomputed, the table only opens the gate.
+ * No atomics: a lane's rank comes from ballots over its wavefront and the four wavefront
+ * totals.  A column's records depend neither on the columns that share its call, nor on
+ * stk_iso_tile (the columns a workgroup takes in turn, 1..32, 0 = the default 16), nor on
+ * alignment beyond 8 bytes (the caller offsets the pointers for a column range).
+ * Refused with the outputs untouched and the argument named in stk_last_error: a null
+ * pointer, n_cols < 1, M != n_free, row_stride below n_cols, a NaN threshold, n_out < 0;
+ * stk_iso_tile refuses values outside its range.
+ * Out of scope: times between nodes, several thresholds per call, joining the pieces into
+ * polylines or surfaces, orientation, sub-regions of the mesh, test-space vectors. */
+int stk_iso_width(int32_t d);
+int stk_iso_count(void *stream, stk_curves_plan *plan, int64_t M, int32_t n_cols,
+                  const double *slab, int64_t row_stride, double threshold, int64_t *counts);
+int stk_iso_fill(void *stream, stk_curves_plan *plan, int64_t M, int32_t n_cols,
+                 const double *slab, int64_t row_stride, double threshold,
+                 const int64_t *counts, const int64_t *first, int64_t n_out, double *out);
+int stk_iso_tile(int32_t cols);
+
 /* ---- solidification maps: gradient, cooling rate and front speed per cell ----------------
  * What happens at the freezing front of a trial-space slab, per CELL: when the mean of the
  * cell last dropped to or below a threshold, how fast it was cooling and what grad u_h was at

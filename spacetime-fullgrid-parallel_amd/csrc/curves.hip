@@ -29,20 +29,9 @@
 // and no kernel here calls fma.
 #include <algorithm>
 
-#include "p1_mesh.h"
+#include "curves_plan.h"
 
 #pragma clang fp contract(off)
-
-struct stk_curves_plan {
-    int32_t d;
-    int64_t nv, nc, n_free, n_tiles, n_work;
-    p1_mesh_dev mesh;
-    double *vol;     // [nc]
-    double *grad;    // [nc][d + 1][d]
-    uint8_t *faces;  // [nc]: bit a = the face opposite vertex a is a boundary face
-    double *work;    // [rows][batch columns][n_work] partials of a batch in flight
-    int64_t work_doubles;
-};
 
 namespace {
 
@@ -111,12 +100,6 @@ __device__ inline void tile_tree(const double *red, int tid, Put put)
     }
 }
 
-// a point in registers: a vertex of the cell or a cut on one of its edges
-template <int D>
-struct pt {
-    double x[D];
-};
-
 // |det| of the edge vectors x_r - x_0 of a sub-simplex, over d!: the expressions of
 // p1_simplex_of and p1_volume (x3 is not read for a triangle)
 template <int D>
@@ -155,9 +138,7 @@ template <int D>
 __device__ inline void zone_of_cell(const double (&U)[D + 1], const double (*P)[D], double v, double theta,
                                     double &measure, double (&moment)[D], double (&lo)[D], double (&hi)[D])
 {
-    int n = 0;
-#pragma unroll
-    for (int a = 0; a <= D; ++a) n += U[a] > theta ? 1 : 0;
+    const int n = cut_above<D>(U, theta);
     measure = 0.0;
 #pragma unroll
     for (int j = 0; j < D; ++j) moment[j] = 0.0, lo[j] = __builtin_inf(), hi[j] = -__builtin_inf();
@@ -178,45 +159,10 @@ __device__ inline void zone_of_cell(const double (&U)[D + 1], const double (*P)[
         }
         return;
     }
-    // the order: a stable partition, above ones first, by the adjacent exchanges of a bubble
-    // sort on the flag -- selects on whole records, no indexed access
-    double W[D + 1], Q[D + 1][D];
-    bool up[D + 1];
-#pragma unroll
-    for (int a = 0; a <= D; ++a) {
-        W[a] = U[a], up[a] = U[a] > theta;
-#pragma unroll
-        for (int j = 0; j < D; ++j) Q[a][j] = P[a][j];
-    }
-#pragma unroll
-    for (int pass = D; pass >= 1; --pass) {
-#pragma unroll
-        for (int i = 0; i < pass; ++i) {
-            const bool swap = !up[i] && up[i + 1];
-            const double w0 = W[i], w1 = W[i + 1];
-            W[i] = swap ? w1 : w0, W[i + 1] = swap ? w0 : w1;
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                const double q0 = Q[i][j], q1 = Q[i + 1][j];
-                Q[i][j] = swap ? q1 : q0, Q[i + 1][j] = swap ? q0 : q1;
-            }
-            const bool u0 = up[i], u1 = up[i + 1];
-            up[i] = swap ? u1 : u0, up[i + 1] = swap ? u0 : u1;
-        }
-    }
-    const auto vertex = [&](int a) {
-        pt<D> c;
-#pragma unroll
-        for (int j = 0; j < D; ++j) c.x[j] = Q[a][j];
-        return c;
-    };
-    const auto cut = [&](int a, int b) {
-        const double s = (W[a] - theta) / (W[a] - W[b]);
-        pt<D> c;
-#pragma unroll
-        for (int j = 0; j < D; ++j) c.x[j] = Q[a][j] + s * (Q[b][j] - Q[a][j]);
-        return c;
-    };
+    // the order q_0 .. q_d and the cuts: curves_plan.h, shared with the isotherms
+    const cell_cut<D> q(U, P, theta);
+    const auto vertex = [&](int a) { return q.vertex(a); };
+    const auto cut = [&](int a, int b) { return q.cut(a, b); };
     const auto widen = [&](const pt<D> &x) {
 #pragma unroll
         for (int j = 0; j < D; ++j) {

@@ -1,6 +1,6 @@
 // The simplicial P1 mesh as the load engine (load_dev.hip), the error norms
-// (err_norms.hip), the sampler (sample.hip), the time curves (curves.hip) and the
-// solidification scan (solid.hip) see it: THE
+// (err_norms.hip), the sampler (sample.hip), the time curves and the isotherms (curves.hip,
+// iso.hip) and the solidification scan (solid.hip) see it: THE
 // definition of the simplex geometry, of |T| and the gradients per cell, of the quadrature
 // points of a cell and of the time bracket of a pair, and the host side of a plan -- the
 // opening checks (p1_plan_open: the arguments, the mesh, the vertex -> slab-row map), the int32

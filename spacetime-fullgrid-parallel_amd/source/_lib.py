@@ -286,6 +286,10 @@ _PROTOTYPES = {
     'stk_curves_eval': (ctypes.c_int, [c_p, c_p, c_i64, c_i32, c_p, c_i64, c_f64, c_i64, c_p]),
     'stk_curves_tile': (ctypes.c_int, [c_i32]),
     'stk_curves_batch': (ctypes.c_int, [c_i64]),
+    'stk_iso_width': (ctypes.c_int, [c_i32]),
+    'stk_iso_count': (ctypes.c_int, [c_p, c_p, c_i64, c_i32, c_p, c_i64, c_f64, c_p]),
+    'stk_iso_fill': (ctypes.c_int, [c_p, c_p, c_i64, c_i32, c_p, c_i64, c_f64, c_p, c_p, c_i64, c_p]),
+    'stk_iso_tile': (ctypes.c_int, [c_i32]),
     'stk_solid_rows': (ctypes.c_int, [c_i32]),
     'stk_solid_tile_rows': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
     'stk_solid_plan_create': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_i64, c_p, ctypes.POINTER(c_p)]),

@@ -59,6 +59,13 @@ SOLID_OPTIONS = (
      ' front_speed, n_solid, max_grad, t_max_grad per cell, with the centroids) to this .npz; needs --solid_threshold'),
     ('solid_threshold', float, None, 'threshold whose last downward crossing by a cell\'s mean is its solidification'),
 )
+# ... and for the isotherms of the solution (the level-set segments or triangles per time node)
+ISO_OPTIONS = (
+    ('iso_out', str, None, 'write the isotherm {u_h = threshold} of the solution at time nodes (nodes, times, offsets,'
+     ' vertices, grad, cell, measure, measure_at, flux_at) to this .npz; needs --iso_threshold'),
+    ('iso_threshold', float, None, 'threshold of the isotherms'),
+    ('iso_every', int, 1, 'every K-th time node from 0 (default 1: every node)'),
+)
 
 
 def device_mb():
@@ -153,31 +160,36 @@ def take_options(args, options, wanted):
 
 
 # what a solve driver can do with its solution: (name, options, the flags that ask for it)
-POST_OPTIONS = SAMPLE_OPTIONS + TRACK_OPTIONS + HISTORY_OPTIONS + CURVES_OPTIONS + SOLID_OPTIONS
+POST_OPTIONS = SAMPLE_OPTIONS + TRACK_OPTIONS + HISTORY_OPTIONS + CURVES_OPTIONS + SOLID_OPTIONS + ISO_OPTIONS
 _POST = (('sample', SAMPLE_OPTIONS, ('sample_out', 'error_norms')), ('track', TRACK_OPTIONS, ('track_out',)),
          ('history', HISTORY_OPTIONS, ('history_out',)), ('curves', CURVES_OPTIONS, ('curves_out',)),
-         ('solid', SOLID_OPTIONS, ('solid_out',)))
+         ('solid', SOLID_OPTIONS, ('solid_out',)), ('iso', ISO_OPTIONS, ('iso_out',)))
 
 
 def take_post_options(args):
     """(the parsed command line without POST_OPTIONS -- never constructor arguments --, asked):
-    asked[name] = the options of 'sample', 'track', 'history', 'curves', 'solid', None where
-    the command line does not ask for it.  --solid_out without --solid_threshold ends the run
-    as an argument error does, before anything is built."""
+    asked[name] = the options of 'sample', 'track', 'history', 'curves', 'solid', 'iso', None
+    where the command line does not ask for it.  --solid_out without --solid_threshold, and
+    --iso_out without --iso_threshold or with an --iso_every below 1, end the run as an
+    argument error does, before anything is built."""
     asked = {}
     for name, options, wanted in _POST:
         args, asked[name] = take_options(args, options, wanted)
     if asked['solid'] is not None and asked['solid'].solid_threshold is None:
         raise SystemExit('--solid_out needs --solid_threshold: the maps are those of one threshold')
+    if asked['iso'] is not None and asked['iso'].iso_threshold is None:
+        raise SystemExit('--iso_out needs --iso_threshold: the isotherms are those of one threshold')
+    if asked['iso'] is not None and asked['iso'].iso_every < 1:
+        raise SystemExit('--iso_every must be at least 1')
     return args, asked
 
 
 def run_post(heat, solution, asked, rank=0):
     """After the solve, what `asked` (take_post_options) asks for, in the fixed order sample,
-    track, history, curves, solid, error norms; every step is collective.  Returns the record
+    track, history, curves, solid, iso, error norms; every step is collective.  Returns the record
     of the error norms, None where there is none."""
     for name, write in (('sample', write_samples), ('track', write_track), ('history', write_history),
-                        ('curves', write_curves), ('solid', write_solid)):
+                        ('curves', write_curves), ('solid', write_solid), ('iso', write_isotherms)):
         if asked[name] is not None and getattr(asked[name], name + '_out'):
             write(heat, solution, asked[name], rank)
     if asked['sample'] is not None and asked['sample'].error_norms:
@@ -259,6 +271,16 @@ def write_solid(heat, solution, args, rank=0):
     mesh = heat._sample_meshes[0]
     centroids = np.asarray(mesh.points, dtype=np.float64)[np.asarray(mesh.cells, dtype=np.int64)].mean(axis=1)
     _write_npz(args.solid_out, rank, centroids=centroids, threshold=float(args.solid_threshold), **got)
+    return got
+
+
+def write_isotherms(heat, solution, args, rank=0):
+    """--iso_out: the isotherm {u_h = iso_threshold} of the solution at every iso_every-th time
+    node from 0, written by rank 0 as an .npz with threshold and one array per entry of
+    heat.isotherms.  Collective; works for both solve drivers."""
+    nodes = list(range(0, heat._sample_meshes[1].nv, args.iso_every))
+    got = heat.isotherms(solution, threshold=args.iso_threshold, nodes=nodes)
+    _write_npz(args.iso_out, rank, threshold=float(args.iso_threshold), **got)
     return got
 
 

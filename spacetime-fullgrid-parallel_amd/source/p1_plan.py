@@ -5,7 +5,7 @@ side).
   plan.  SamplePlan (sampling.py), ErrorPlan (error_norms.py), CurvesPlan (time_curves.py),
   SolidPlan (solidification.py) and DeviceLoadPlan (assembly.py) each hold one handle.
 * ``threshold_value``, ``check_points_shape``, ``field_names``: the pieces the
-  ``check_arguments`` of history.py, time_curves.py and solidification.py are built from;
+  ``check_arguments`` of history.py, time_curves.py, solidification.py and isotherms.py are built from;
   they raise ValueError and touch no GPU.
 * ``time_step``: the time mesh of a vector, the uniform one of [0, 1] by default.
 * ``scan_down_the_ranks``: a scan along time whose state travels from rank to rank (the

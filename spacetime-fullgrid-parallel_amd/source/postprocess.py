@@ -1,6 +1,7 @@
 """What both solve drivers (heateq.py, heateq_mpi.py) offer on a solution once it is there:
-sampling, its adjoint, the history maps, the time curves, the solidification maps and the
-error norms -- the eight public methods, once, with the plans they build on first use.
+sampling, its adjoint, the history maps, the time curves, the solidification maps, the
+isotherms and the error norms -- the nine public methods, once, with the plans they build on
+first use.
 
 A driver inherits ``PostProcessing``, calls ``_init_postprocessing`` from its constructor and
 supplies what truly differs as two hooks: how `u` becomes a trial-space device vector
@@ -50,7 +51,7 @@ class PostProcessing:
         self._trial_vector(u, 'sampling')
         return self._sample_plan()
 
-    # ---- the eight methods ----------------------------------------------------------------------
+    # ---- the nine methods -----------------------------------------------------------------------
     def sample(self, u, times, points, field='u'):
         """u_h(t_k, x_p) of a trial-space vector `u` (KronVectorMPI: a solution, an iterate)
         at `times` (n_k,) in [0, T] and `points` (n_p, d) -- NumPy array, device tensor, or
@@ -190,6 +191,35 @@ class PostProcessing:
         if points is not None:
             self._sample_plan()
         return solidification_maps(self, u, threshold, points, fields)
+
+    def isotherms(self, u, threshold, nodes=None, max_bytes=2**30):
+        """The isotherm {u_h = threshold} of a trial-space vector `u` (KronVectorMPI) at the time
+        nodes `nodes` (None: all N; or strictly ascending ints in [0, N)), as the segments (d =
+        2) or triangles (d = 3) in which it cuts the cells -- exact for the P1 function, the cut
+        of the zone of ``time_curves`` (source/isotherms.py, csrc/iso.hip): a dict of device
+        tensors 'nodes' ((n_k,) int64) and 'times' ((n_k,), float(k) * h), 'offsets' ((n_k + 1,)
+        int64: the pieces of nodes[k] are the rows offsets[k] .. offsets[k + 1]), 'vertices'
+        ((n, d, d): the d vertices of a piece), 'grad' ((n, d): grad u_h in the piece's cell;
+        the orientation of a piece is not promised, this orients it), 'cell' ((n,) int64),
+        'measure' ((n,): the length or area of a piece, the square root taken in torch),
+        'measure_at' ((n_k,): the length or area of the isotherm) and 'flux_at' ((n_k,): the sum
+        of measure |grad u_h|, the heat crossing the isotherm per unit conductivity).  The
+        pieces of a node come in the mesh's cell order.  A vertex AT the threshold is not above,
+        the rule of ``time_curves``; boundary vertices carry the value 0; +-inf gives no piece.
+        COLLECTIVE and independent of the number of ranks, bit for bit: a rank counts and fills
+        the nodes it owns, the places of the records come from an exclusive scan of the int64
+        counts per (node, tile of 256 cells), no atomics, the per-node sums are trees of one
+        fixed shape, and two all-reduces with one non-zero contributor per entry give every
+        rank all of it.  A missing or NaN threshold or bad `nodes` raises ValueError before
+        anything touches the GPU; so does, before anything is allocated, a result of more than
+        `max_bytes` bytes, naming the number of pieces.  The plan is the one of ``time_curves``
+        (``curves_plan``), built by the first call of either.  Test-space vectors are refused.
+        Out of scope: times between the nodes, several thresholds in one call, joining the
+        pieces into polylines, orientation, sub-regions of the domain.  The serial driver also
+        takes `u` as a flat NumPy vector or a device vector and returns the same dict."""
+        from .isotherms import check_arguments, isotherms
+        check_arguments(threshold, nodes, self._sample_meshes[1].nv, max_bytes)  # before an upload or a plan
+        return isotherms(self, self._trial_vector(u, 'isotherms()'), threshold, nodes, max_bytes)
 
     def error_norms(self, u, exact=None, exact_grad=None, times=None):
         """|| u - u_h || of a trial-space vector `u` (KronVectorMPI) against `exact`
