@@ -1642,6 +1642,63 @@ int stk_solid_scan(void *stream, stk_solid_plan *plan, int64_t M, int32_t n_cols
                    double threshold, int32_t fresh, double *state);
 int stk_solid_tile(int32_t cols, int32_t lds_kib);
 
+/* ---- level transfer: a coarse trial-space slab prolonged to a finer discretisation ------
+ * The first engine that connects two discretisations: the trial-space vector of a coarser
+ * space mesh (one red refinement fewer, its vertices a prefix of the finer mesh's) and of a
+ * coarser time mesh (N_f - 1 = 2^a (N_c - 1) elements, a >= 0) as the vector of the finer
+ * trial space that represents the SAME function -- P1 in space, piecewise linear in time.
+ * All arithmetic is rounded term by term (no fused multiply-adds).
+ *
+ * SPACE, one level.  A plan holds parents [M_fine][2] (int32): per free row of the fine level
+ * the free rows of the coarse level it interpolates, -1 for a parent on the boundary (value
+ * 0).  With uc the coarse slab and q a coarse time node:
+ *     parents[i] = (p, p):   s_i(q) = uc[p, q]                   a copy, no arithmetic
+ *     otherwise:             s_i(q) = (A + B) * 0.5              A, B = the parents' values,
+ *                                                                0.0 for an absent one
+ *                                                                (both absent, the pair
+ *                                                                (-1, -1): 0.0)
+ * TIME, a levels in one shot.  The fine node k = k_first + c has q = k >> a and
+ * rem = k & (2^a - 1):
+ *     rem == 0:   out[i, c] = s_i(q)                             column q + 1 is NOT read
+ *     otherwise:  w1 = rem / 2^a,  w0 = 1.0 - w1  (both exact),
+ *                 out[i, c] = w0 * s_i(q) + w1 * s_i(q + 1)      two rounded products, one
+ *                                                                rounded sum
+ * (A chain of half-steps in time would round differently: time goes in one shot.  Several
+ * space levels are chained by the caller: a = 0 on the coarse time mesh for all but the
+ * last level, which carries all of the time refinement and writes the big slab once.)
+ *
+ * Layouts: both slabs are this library's, time contiguous -- uc[j*ldc + (q - qc_first)] for
+ * q - qc_first < n_cc, out[i*ld + c] for c < n_cols; columns c >= n_cols of out (the pad of
+ * an odd n_loc) are never written.  out and uc need only be 8-byte aligned (a rank's window
+ * may start at an odd column).  All offsets are 64-bit; no atomics; nothing is allocated and
+ * nothing synchronises.  NaN and +-inf in uc give what the rules give.
+ *
+ * stk_transfer_plan_create checks every index -- in [-1, M_coarse); (-1, -1), the vertex
+ * between two boundary vertices, not in a row i < M_coarse: in the hierarchical numbering those
+ * are the coarse level's own vertices, which copy and need a row to copy; M_coarse = 0 is
+ * allowed -- and uploads the table to the current device: after that the
+ * kernel reads no row outside [0, M_coarse), whatever it is given.  stk_transfer_prolong
+ * refuses (non-zero, stk_last_error names the argument, out untouched): a null plan, uc or
+ * out, a outside [0, STK_TRANSFER_MAX_A], negative sizes or node numbers, ldc < n_cc,
+ * ld < n_cols, and a coarse window [qc_first, qc_first + n_cc) that does not cover every
+ * column the rules read -- q of the first and of the last fine column, and q + 1 of the
+ * last one only if its rem != 0.  n_cols == 0 or M_fine == 0 is a no-op.
+ *
+ * stk_transfer_tile sets the launch form for the calls that follow, process-wide
+ * (measurement and tests; results never depend on it): `rows` of the fine level per
+ * workgroup -- 64, 128 or 256 -- and the LDS a workgroup may take in KiB, 1..64, which
+ * sets the fine columns per chunk (at least one); 0 for either = the default.  Anything
+ * else is refused and changes nothing. */
+#define STK_TRANSFER_MAX_A 8
+typedef struct stk_transfer_plan stk_transfer_plan;
+int stk_transfer_plan_create(int64_t M_fine, int64_t M_coarse, const int32_t *parents,
+                             stk_transfer_plan **out);
+int stk_transfer_plan_destroy(stk_transfer_plan *plan);
+int stk_transfer_tile(int32_t rows, int32_t lds_kib);
+int stk_transfer_prolong(void *stream, const stk_transfer_plan *plan, int32_t a,
+                         const double *uc, int64_t ldc, int64_t qc_first, int32_t n_cc,
+                         double *out, int64_t ld, int64_t k_first, int32_t n_cols);
+
 /* ---- plan construction on the host threads: processing order and union pattern ---
  * stk_tile_order: the mesh-tile order of n dofs with coordinates coords [n][d]
  * (d = 2 or 3): the bounding box cut into cubes of edge `side` from the corner `lo`

@@ -119,7 +119,7 @@ class HeatEquation(PostProcessing):
         self.u0_x = space_load(mesh_space, data['u0'])
         self.f = self.BT @ (self.K @ self.g_vec) + np.kron(u0_t, self.u0_x)
 
-    def solve(self, callback=None, on_host=False, rhs=None):
+    def solve(self, callback=None, on_host=False, rhs=None, x0=None):
         """PCG on the wavelet-transformed system; returns (u, iterations).  The
         right-hand side goes to the device once and the solution comes back once: in
         between, every vector of the iteration is device-resident (the callback sees
@@ -128,13 +128,19 @@ class HeatEquation(PostProcessing):
         PCIe per operator apply.  `rhs`: another right-hand side on the trial space in
         place of f -- a flat NumPy vector or a device vector (what
         ``sample_along_adjoint`` returned: S^-1 E^T r is the gradient of a point-data
-        misfit)."""
+        misfit).  `x0`: a start -- a flat NumPy vector or a device vector of the trial space
+        (``prolong_from`` of a coarser level's solution, the solution of a nearby right-hand
+        side) -- the correction form, S e = f - S x0 solved from zero, returns
+        (x0 + e, iterations); the callback sees the correction's PCG.  One more apply of S;
+        without x0 nothing changes."""
         from source.linop import _is_device_vector
         f = self.f if rhs is None else rhs
         if _is_device_vector(f):
             assert f.N == self.N and f.M == self.M, 'rhs= takes a vector of the trial space'
         else:
             assert np.size(f) == self.N * self.M, 'rhs= takes a vector of the trial space'
+        if x0 is not None:
+            return self._solve_from(x0, f, callback, on_host)
         if on_host:
             f = host_vector(f) if _is_device_vector(f) else f
             w, iters = PCG(self.WT_S_W, self.P, self.WT @ f, callback=callback)
@@ -142,6 +148,23 @@ class HeatEquation(PostProcessing):
         f = f if _is_device_vector(f) else device_vector(f, self.N)
         w, iters = PCG(self.WT_S_W, self.P, self.WT @ f, callback=callback)
         return host_vector(self.W @ w), iters
+
+    def _solve_from(self, x0, f, callback, on_host):
+        """solve() with a start: PCG on S e = f - S x0 from zero, (x0 + e, iterations)."""
+        from source.linop import _is_device_vector
+        if _is_device_vector(x0):
+            assert x0.N == self.N and x0.M == self.M, 'x0= takes a vector of the trial space'
+        else:
+            assert np.size(x0) == self.N * self.M, 'x0= takes a vector of the trial space'
+        if on_host:
+            x0 = host_vector(x0) if _is_device_vector(x0) else np.asarray(x0, dtype=np.float64).reshape(-1)
+            f = host_vector(f) if _is_device_vector(f) else f
+            w, iters = PCG(self.WT_S_W, self.P, self.WT @ (f - self.S @ x0), callback=callback)
+            return x0 + self.W @ w, iters
+        x0 = x0 if _is_device_vector(x0) else device_vector(x0, self.N)
+        f = f if _is_device_vector(f) else device_vector(f, self.N)
+        w, iters = PCG(self.WT_S_W, self.P, self.WT @ (f - self.S @ x0), callback=callback)
+        return host_vector(x0 + self.W @ w), iters
 
     def errors(self, u):
         """(algebraic error of u in the X-norm, error in Y') as the reference's
@@ -187,6 +210,7 @@ def main(argv=None):
         parser.add_argument('--' + flag, type=kind, default=default, help=text)
     args, asked = driver.take_post_options(parser.parse_args(argv))
     print('Arguments: %s' % args)
+    levels = [] if asked['nested'] is None else driver.nested_levels(args.J_time, args.J_space, asked['nested'].nested)
     print('\n\nCreating HeatEquation with %d time refines and %d space refines.'
           % (args.J_time, args.J_space))
     heat = HeatEquation(**vars(args))
@@ -194,7 +218,13 @@ def main(argv=None):
         driver.require_path(heat, asked['track'])
     print('Size of time mesh: %d dofs. Size of space mesh: %d dofs' % (heat.N, heat.M))
     print('Solving: ', end='')
-    u, iters = heat.solve(callback=lambda w, residual, k: print('.', end='', flush=True))
+    progress = lambda w, residual, k: print('.', end='', flush=True)  # noqa: E731
+    if levels:
+        u, iters, _ = driver.solve_nested(
+            heat, lambda J_time, J_space: HeatEquation(**dict(vars(args), J_time=J_time, J_space=J_space)), levels,
+            callback=progress)
+    else:
+        u, iters = heat.solve(callback=progress)
     print('Done in %d  PCG steps. X-norm algebraic error: %s. Error in Yprime: %s\n'
           % ((iters,) + heat.errors(u)))
     driver.run_post(heat, u, asked)  # this driver keeps no record: the line of the error norms is the report

@@ -507,7 +507,7 @@ class HeatEquationMPI(PostProcessing):
         out = self.Kinv_x.apply(y.buf, n_loc=y.n_loc)
         return KronVectorMPI.around(self.dofs_test, element_block_mix(self.dofs_test, self._minv_blocks, out))
 
-    def solve(self, callback=None, history=None, eps=1e-6, kmax=100000, rhs=None):
+    def solve(self, callback=None, history=None, eps=1e-6, kmax=100000, rhs=None, x0=None):
         """PCG on the wavelet-transformed system with the forcing's right-hand side
         (reference heateq.py:146-150); returns (u = W w, iterations).  `eps`, `kmax`: PCG's
         stopping rule (r.Pr < eps^2; the reference's 1e-6 by default) -- an algebraic error of
@@ -515,13 +515,21 @@ class HeatEquationMPI(PostProcessing):
         smaller eps removes it.  `rhs`: another right-hand side on the trial space (a
         KronVectorMPI, e.g. what ``sample_along_adjoint`` returned: S is symmetric, so
         S^-1 E^T r is the gradient of a point-data misfit) in place of the forcing's f; with
-        it a problem without forcing can call solve() too."""
+        it a problem without forcing can call solve() too.  `x0`: a start (a KronVectorMPI of
+        the trial space: ``prolong_from`` of a coarser level's solution, the solution of a
+        nearby right-hand side) -- the correction form, S e = f - S x0 solved from zero, returns
+        (x0 + e, iterations); `history`, `callback` and the stopping rule are those of the
+        correction's PCG.  One more apply of S; without x0 nothing changes."""
         f = self.f if rhs is None else rhs
         assert f is not None, 'solve() is the path of a problem with forcing; without: PCG on rhs'
         if rhs is not None:
             assert rhs.dofs_distr.N == self.N and rhs.M == self.M, 'rhs= takes a vector of the trial space'
+        if x0 is not None:
+            assert isinstance(x0, KronVectorMPI) and x0.dofs_distr.N == self.N and x0.M == self.M, \
+                'x0= takes a vector of the trial space'
+            f = f - self.S @ x0
         w, iters = PCG(self.WT_S_W, self.P, self.WT @ f, eps=eps, kmax=kmax, callback=callback, history=history)
-        return self.W @ w, iters
+        return (self.W @ w if x0 is None else x0 + self.W @ w), iters
 
     def errors(self, u):
         """(algebraic error r.Pr of u in the X-norm with r = f - S u, error in Y'
@@ -558,6 +566,8 @@ def main(argv=None):
                                 '(2.3x slower than fast)')] + list(driver.POST_OPTIONS))
     args, asked = driver.take_post_options(args)
     comm, rank, size = driver.start(args)
+    levels = [] if asked['nested'] is None else driver.nested_levels(args.J_time, args.J_space,
+                                                                    asked['nested'].nested, size)
     heat = HeatEquationMPI(**driver.solver_arguments(args))
     if asked['track'] is not None:
         driver.require_path(heat, asked['track'])
@@ -585,7 +595,15 @@ def main(argv=None):
     comm.Barrier()
     began = MPI.Wtime()
     history = []
-    if heat.f is None:
+    if levels:
+        # nested iteration: the coarser problems first, each from the prolonged solution of
+        # the one before; solve_time covers their set-up too
+        solution, iters, per_level = driver.solve_nested(
+            heat, lambda J_time, J_space: HeatEquationMPI(**dict(driver.solver_arguments(args), J_time=J_time,
+                                                                 J_space=J_space)),
+            levels, rank, callback=progress, history=history)
+        record.update(nested=per_level)
+    elif heat.f is None:
         solution, iters = PCG(heat.WT_S_W, heat.P, heat.rhs, callback=progress,
                               history=history)
     else:

@@ -298,6 +298,10 @@ _PROTOTYPES = {
     'stk_solid_tile': (ctypes.c_int, [c_i32, c_i32]),
     'stk_solid_cell_order': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_p]),
     'stk_solid_order': (ctypes.c_int, [c_i32]),
+    'stk_transfer_plan_create': (ctypes.c_int, [c_i64, c_i64, c_p, ctypes.POINTER(c_p)]),
+    'stk_transfer_plan_destroy': (ctypes.c_int, [c_p]),
+    'stk_transfer_tile': (ctypes.c_int, [c_i32, c_i32]),
+    'stk_transfer_prolong': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i64, c_i32]),
     'stk_tile_order': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_f64, c_p]),
     'stk_csr_union_count': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_p]),
     'stk_csr_union_fill': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),

@@ -66,6 +66,11 @@ ISO_OPTIONS = (
     ('iso_threshold', float, None, 'threshold of the isotherms'),
     ('iso_every', int, 1, 'every K-th time node from 0 (default 1: every node)'),
 )
+# ... and for nested iteration: the solve started from the prolonged solution of coarser levels
+NESTED_OPTIONS = (
+    ('nested', int, 0, 'solve the L coarser problems (J_time - l, J_space - l), l = L .. 1, first, from the coarsest up,'
+     ' each started from the prolonged solution of the one before (prolong_from, solve(x0=)); default 0: none'),
+)
 
 
 def device_mb():
@@ -160,18 +165,20 @@ def take_options(args, options, wanted):
 
 
 # what a solve driver can do with its solution: (name, options, the flags that ask for it)
-POST_OPTIONS = SAMPLE_OPTIONS + TRACK_OPTIONS + HISTORY_OPTIONS + CURVES_OPTIONS + SOLID_OPTIONS + ISO_OPTIONS
+POST_OPTIONS = (SAMPLE_OPTIONS + TRACK_OPTIONS + HISTORY_OPTIONS + CURVES_OPTIONS + SOLID_OPTIONS + ISO_OPTIONS
+                + NESTED_OPTIONS)
 _POST = (('sample', SAMPLE_OPTIONS, ('sample_out', 'error_norms')), ('track', TRACK_OPTIONS, ('track_out',)),
          ('history', HISTORY_OPTIONS, ('history_out',)), ('curves', CURVES_OPTIONS, ('curves_out',)),
-         ('solid', SOLID_OPTIONS, ('solid_out',)), ('iso', ISO_OPTIONS, ('iso_out',)))
+         ('solid', SOLID_OPTIONS, ('solid_out',)), ('iso', ISO_OPTIONS, ('iso_out',)),
+         ('nested', NESTED_OPTIONS, ('nested',)))
 
 
 def take_post_options(args):
     """(the parsed command line without POST_OPTIONS -- never constructor arguments --, asked):
-    asked[name] = the options of 'sample', 'track', 'history', 'curves', 'solid', 'iso', None
-    where the command line does not ask for it.  --solid_out without --solid_threshold, and
-    --iso_out without --iso_threshold or with an --iso_every below 1, end the run as an
-    argument error does, before anything is built."""
+    asked[name] = the options of 'sample', 'track', 'history', 'curves', 'solid', 'iso', 'nested',
+    None where the command line does not ask for it.  --solid_out without --solid_threshold,
+    --iso_out without --iso_threshold or with an --iso_every below 1, and a negative --nested
+    end the run as an argument error does, before anything is built."""
     asked = {}
     for name, options, wanted in _POST:
         args, asked[name] = take_options(args, options, wanted)
@@ -181,7 +188,46 @@ def take_post_options(args):
         raise SystemExit('--iso_out needs --iso_threshold: the isotherms are those of one threshold')
     if asked['iso'] is not None and asked['iso'].iso_every < 1:
         raise SystemExit('--iso_every must be at least 1')
+    if asked['nested'] is not None and asked['nested'].nested < 0:
+        raise SystemExit('--nested must be at least 0')
     return args, asked
+
+
+def nested_levels(J_time, J_space, nested, size=1):
+    """[(J_time - l, J_space - l) for l = nested .. 1]: the coarser problems of --nested, the
+    coarsest first.  Ends the run, before anything is built, where a level cannot be built:
+    a negative number of refines, or fewer time nodes than ranks."""
+    levels = [(J_time - l, J_space - l) for l in range(int(nested), 0, -1)]
+    for jt, js in levels:
+        if jt < 0 or js < 0:
+            raise SystemExit('--nested %d: there is no level (J_time = %d, J_space = %d)' % (nested, jt, js))
+        if 2**jt + 1 < size:
+            raise SystemExit('--nested %d: the level J_time = %d has %d time nodes, fewer than the %d ranks'
+                             % (nested, jt, 2**jt + 1, size))
+    return levels
+
+
+def solve_nested(heat, build, levels, rank=0, **solve_arguments):
+    """Nested iteration: ``build(J_time, J_space)`` makes the driver object of each of `levels`
+    (nested_levels: the coarsest first); every level is solved from the prolonged solution of
+    the one before it (heat.prolong_from, solve(x0=)), the coarsest from zero, `heat` last.
+    Rank 0 prints one line with the iterations per level.  `solve_arguments` (callback,
+    history, ...) go to the LAST solve.  Returns (u, iterations) of `heat`, and the list of
+    (J_time, J_space, iterations) of all levels; collective."""
+    if heat.f is None:  # before a coarser problem is built
+        raise SystemExit('--nested: solve() is the path of a problem with forcing; this problem has none')
+    before, u, counts = None, None, []
+    for number, level in enumerate(list(levels) + [None]):
+        this = heat if level is None else build(*level)
+        x0 = None if before is None else this.prolong_from(before, u)
+        u, iters = this.solve(x0=x0, **(solve_arguments if level is None else {}))
+        mesh_space, mesh_time = this._sample_meshes
+        counts.append((int(mesh_time.N_el).bit_length() - 1, mesh_space.J - 1, iters))
+        if rank == 0:
+            print('\nNested level %d of %d (J_time = %d, J_space = %d): %d PCG steps%s.'
+                  % ((number, len(levels)) + counts[-1] + ('' if x0 is not None else ', from zero',)))
+        before = this
+    return u, iters, counts
 
 
 def run_post(heat, solution, asked, rank=0):

@@ -1,7 +1,7 @@
 """What both solve drivers (heateq.py, heateq_mpi.py) offer on a solution once it is there:
 sampling, its adjoint, the history maps, the time curves, the solidification maps, the
-isotherms and the error norms -- the nine public methods, once, with the plans they build on
-first use.
+isotherms, the error norms and the prolongation of a coarser level's vector -- the ten public
+methods, once, with the plans they build on first use.
 
 A driver inherits ``PostProcessing``, calls ``_init_postprocessing`` from its constructor and
 supplies what truly differs as two hooks: how `u` becomes a trial-space device vector
@@ -21,6 +21,7 @@ class PostProcessing:
         self._sample_meshes = (mesh_space, mesh_time)
         self._exact = (data.get('exact'), data.get('exact_grad'))
         self.sample_plan = self.error_plan = self.curves_plan = self.solid_plan = None
+        self.transfer_plans = {}  # per coarse discretisation, built by the first prolong_from() of it
 
     # ---- what a driver supplies -----------------------------------------------------------------
     def _trial_vector(self, u, who):
@@ -51,7 +52,7 @@ class PostProcessing:
         self._trial_vector(u, 'sampling')
         return self._sample_plan()
 
-    # ---- the nine methods -----------------------------------------------------------------------
+    # ---- the ten methods ------------------------------------------------------------------------
     def sample(self, u, times, points, field='u'):
         """u_h(t_k, x_p) of a trial-space vector `u` (KronVectorMPI: a solution, an iterate)
         at `times` (n_k,) in [0, T] and `points` (n_p, d) -- NumPy array, device tensor, or
@@ -242,3 +243,29 @@ class PostProcessing:
             exact_grad = default_grad if exact_grad is None else exact_grad
         assert exact is not None, 'this problem has no exact solution: pass exact='
         return error_norms_collective(self._lazy_plan('error_plan', ErrorPlan), u, exact, exact_grad, times)
+
+    def prolong_from(self, coarse_heat, u_coarse):
+        """P u_c: the trial-space vector `u_coarse` of the COARSER discretisation `coarse_heat`
+        (a driver object of this class on (J_time - a, J_space - s), a, s >= 0, built on the
+        same communicator) as a trial-space vector of THIS discretisation that represents the
+        same function -- P1 in space on the nested meshes, piecewise linear in time -- from one
+        pass on the device (source/transfer.py, csrc/transfer.hip): a fine row copies its coarse
+        row or is (A + B) * 0.5 of its two parents' values (0.0 on the boundary), a fine node
+        k = (q << a) + rem is s(q), or (1.0 - rem / 2^a) * s(q) + (rem / 2^a) * s(q + 1), every
+        operation rounded on its own.  Returns a new KronVectorMPI on this driver's
+        distribution: the start of a nested iteration (``solve(x0=...)``), and with
+        ``time_curves(u - P u_c)['l2_sq']`` the distance || u_h - P u_2h || of two levels.
+        COLLECTIVE and independent of the number of ranks, bit for bit: every rank's coarse
+        columns go into one (M_c, N_c) buffer, one all-reduce with one non-zero contributor per
+        entry gives every rank all of it, and every rank prolongs into the columns it owns.
+        Meshes that are not nested -- the coarse points, boundary flags and parents must be the
+        prefix of the fine ones, T the same, the time elements in a ratio 2^a, a <= 8 -- raise
+        ValueError before anything touches the GPU.  The plan is cached per coarse
+        discretisation (``transfer_plans``) and built by the first call; a run that never asks
+        builds nothing.  Out of scope: the adjoint P^T, injection and restriction, test-space
+        vectors, a neighbour-only exchange of the coarse columns, other time ratios, different
+        coarsest meshes.  The serial driver also takes `u_coarse` as a flat NumPy vector or a
+        device vector and returns a device vector (source.linop.host_vector copies it out;
+        ``solve(x0=...)`` takes it as it is)."""
+        from .transfer import prolong_from
+        return prolong_from(self, coarse_heat, u_coarse)
