@@ -156,8 +156,9 @@ int stk_slab_extract_time_rows(void *stream, int32_t M, int32_t n_rows,
  * KronVectorMPI.permute and of the distributed wavelet transform). */
 int stk_copy_block(void *stream, int64_t rows, int32_t cols, const double *src,
                    int64_t ld_src, double *dst, int64_t ld_dst);
-/* y[i * ld + t] = u_t[t] * u_x[i] (padding zero): the right-hand side
- * u0_t kron u0_x of heateq_mpi.py:189-191 formed on the device. */
+/* y[i * ld + t] = u_t[t] * u_x[i]: the right-hand side u0_t kron u0_x of
+ * heateq_mpi.py:189-191 formed on the device.  All ld columns of every row are
+ * written, those from n_loc on as +0.0 (any ld >= n_loc, odd ones included). */
 int stk_outer(void *stream, int32_t M, int32_t n_loc, int32_t ld,
               const double *u_t, const double *u_x, double *y);
 
@@ -206,14 +207,23 @@ int stk_comm_exchange(stk_comm *comm, void *stream, int32_t n_send,
  * and dia_a / dia_m (either may be NULL) still receive it.  grp (or NULL): keep
  * only the entries whose column lies in an EARLIER dependency group than the row,
  * grp[col] < grp[row] (the zero-start copies of the first sweep of a level visit).
- * *overflow (device int32, zeroed by the caller) receives the longest row if one
- * has more than K entries.
+ * *overflow (device int32, zeroed by the caller) receives the longest kept row if
+ * one has more than K entries; such a row holds its first K kept entries, every
+ * other row is complete.  A row without a diagonal entry gives dia_a = dia_m = 0.
+ * n_pos = 0 returns 0 and touches nothing.
  * stk_csr_galerkin: C = R A P for CSR matrices on the device, one row of C per
  * thread, every sum accumulated in the order SciPy's (R @ A) @ P accumulates it and
  * with separately rounded products and sums -- C is bit for bit the reference's
  * Galerkin matrix.  Row i: row_counts[i] entries at out_indices / out_data
- * [i*cap ...], columns ascending; cap <= 64; *overflow as above.  P = NULL (all
- * three arrays): C = R A alone, the product the restricted residual uses.
+ * [i*cap ...], columns ascending, the slots from row_counts[i] on untouched;
+ * 1 <= cap <= 64.  An entry whose sum is exactly zero is not emitted (csr_matmat's
+ * rule), but a row is held by the columns its products TOUCH -- those whose sum
+ * cancels, and those reached only through an entry of R A that cancelled,
+ * included: *overflow (device int32, zeroed by the caller) receives the largest
+ * such count over the rows where it exceeds cap, and 65 where a row of R A or of
+ * R A P touches more than 64 columns; a row that overflows leaves its count and
+ * its slots unwritten (the caller forms the product on the host then).  P = NULL
+ * (all three arrays): C = R A alone, the product the restricted residual uses.
  * stk_gs_depth_step: one relaxation of the depth of every row in the dependency
  * DAG of a Gauss-Seidel sweep in dof order (forward: row i waits for its
  * neighbours j < i; backward: j > i), depth_out[i] = max depth_in[j] + 1;
@@ -245,8 +255,10 @@ int stk_axpby(void *stream, int64_t n, double a, const double *x, double b,
 /* z = a * x + b * y   (three-operand form, z may alias x or y) */
 int stk_axpbyz(void *stream, int64_t n, double a, const double *x, double b,
                const double *y, double *z);
-/* out[0] = sum x[k] * y[k].  Deterministic two-stage reduction; `work` holds
- * at least stk_dot_work_size() doubles. */
+/* out[0] = sum x[k] * y[k] (n = 0: +0.0, x and y may be NULL).  Deterministic
+ * two-stage reduction; `work` holds at least stk_dot_work_size() doubles, of
+ * which the first min(ceil((n / 2 + 1) / 256), 2048) are written; x and y are
+ * 16-byte aligned. */
 int64_t stk_dot_work_size(void);
 int stk_dot(void *stream, int64_t n, const double *x, const double *y,
             double *work, double *out);

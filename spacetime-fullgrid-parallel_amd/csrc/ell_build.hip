@@ -14,7 +14,15 @@
 //    emits them, then times P -- with separately rounded multiply and add, so that
 //    the coarse matrices are BIT FOR BIT those of the reference's `R @ A @ P`
 //    (the solve's history is sensitive to their last bit).
+//
+// ARITHMETIC: __dmul_rn / __dadd_rn are a plain `*` and `+` in HIP's headers, and the
+// compiler fused them into one v_fmac_f64 per term -- invisible on transfer operators
+// whose entries are 1 and 1/2 (every product exact), a few ulps off SciPy on any others
+// (tests/test_plan_builders_gpu.py, roundings-*).  Contraction is SWITCHED OFF for this
+// file (the pragma and -ffp-contract=off in the Makefile), and no kernel here calls fma.
 #include "stk_common.h"
+
+#pragma clang fp contract(off)
 
 namespace {
 
