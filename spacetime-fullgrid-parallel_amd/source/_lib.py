@@ -11,317 +11,68 @@ import os
 import numpy as np
 import torch
 
+from . import _header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), 'libstk.so')
-
-c_i32, c_i64, c_f64, c_p = (ctypes.c_int32, ctypes.c_int64, ctypes.c_double,
-                            ctypes.c_void_p)
-
-
-# callbacks of stk_pcg_solve (include/stk.h)
-OPERATOR_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                               ctypes.c_void_p, ctypes.c_void_p)
-ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p,
-                                ctypes.POINTER(ctypes.c_double), ctypes.c_int32)
-
-
-class EllPattern(ctypes.Structure):
-    _fields_ = [('M', c_i32), ('K', c_i32), ('ell_idx', c_p),
-                ('row_ids', c_p), ('ovf_indptr', c_p), ('ovf_indices', c_p)]
-
-
-class KronEllTerm(ctypes.Structure):
-    _fields_ = [('tri', c_p), ('ell_vals', c_p), ('ovf_vals', c_p),
-                ('x', c_p), ('x_lo', c_p), ('x_hi', c_p)]
-
-
-class PackPattern(ctypes.Structure):
-    _fields_ = [('M', c_i32), ('K', c_i32), ('col_bits', c_i32),
-                ('n_codes', c_i32), ('n_mats', c_i32),
-                ('rows_per_unit', c_i32), ('n_units', c_i32), ('slots', c_p),
-                ('row_ids', c_p), ('dict', c_p), ('vals', c_p)]
-
-
-class KronPackTerm(ctypes.Structure):
-    _fields_ = [('tri', c_p), ('mat', c_i32)]
-
-
-class CommMsg(ctypes.Structure):
-    _fields_ = [('buf', c_p), ('count', c_i64), ('peer', c_i32)]
-
-
-class EllRows(ctypes.Structure):
-    _fields_ = [('n_pos', c_i32), ('n_rows', c_i32), ('K', c_i32),
-                ('idx', c_p), ('va', c_p), ('vm', c_p), ('row_ids', c_p),
-                ('dia_a', c_p), ('dia_m', c_p), ('diag_free', c_i32)]
-
-
-class CsrHost(ctypes.Structure):
-    _fields_ = [('n_rows', c_i32), ('n_cols', c_i32), ('indptr', c_p),
-                ('indices', c_p), ('data', c_p)]
-
-
-class MGLevel(ctypes.Structure):
-    _fields_ = [('n', c_i32), ('indptr', c_p), ('indices', c_p),
-                ('vals_a', c_p), ('vals_m', c_p), ('diag', c_p),
-                ('n_fwd', c_i32), ('fwd_ptr_host', c_p), ('fwd_rows', c_p),
-                ('n_bwd', c_i32), ('bwd_ptr_host', c_p), ('bwd_rows', c_p),
-                ('p_indptr', c_p), ('p_indices', c_p), ('p_vals', c_p),
-                ('r_indptr', c_p), ('r_indices', c_p), ('r_vals', c_p),
-                ('ell_a', ctypes.POINTER(EllRows)),
-                ('ell_fwd', ctypes.POINTER(EllRows)),
-                ('ell_bwd', ctypes.POINTER(EllRows)),
-                ('ell_p', ctypes.POINTER(EllRows)),
-                ('ell_r', ctypes.POINTER(EllRows)),
-                ('fwd_pos_host', c_p), ('bwd_pos_host', c_p),
-                ('ell_ra', ctypes.POINTER(EllRows)),
-                ('ell_fwd0', ctypes.POINTER(EllRows)),
-                ('n_tile_rows', c_i32), ('fwd_tile_row_host', c_p),
-                ('bwd_tile_row_host', c_p),
-                ('ell_fwd_alt', ctypes.POINTER(EllRows)),
-                ('ell_bwd_alt', ctypes.POINTER(EllRows))]
-
-
-_PROTOTYPES = {
-    'stk_last_error': (ctypes.c_char_p, []),
-    'stk_version': (ctypes.c_int, []),
-    'stk_device_info': (ctypes.c_int, [c_p, c_p, c_p]),
-    'stk_axpby': (ctypes.c_int, [c_p, c_i64, c_f64, c_p, c_f64, c_p]),
-    'stk_axpbyz': (ctypes.c_int, [c_p, c_i64, c_f64, c_p, c_f64, c_p, c_p]),
-    'stk_dot_work_size': (c_i64, []),
-    'stk_dot': (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p, c_p]),
-    'stk_set_tuning': (ctypes.c_int, [ctypes.c_char_p, c_i32]),
-    'stk_partition': (ctypes.c_int, [c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p]),
-    'stk_pcg_work_size': (c_i64, [c_i64]),
-    'stk_pcg_solve': (ctypes.c_int, [
-        c_p, c_i64, OPERATOR_FN, c_p, OPERATOR_FN, c_p, ALLREDUCE_FN, c_p, c_p,
-        c_p, c_f64, c_i32, c_p, c_p, c_p
-    ]),
-    'stk_pcg_slab_work_size': (c_i64, [c_i32, c_i32, c_i32, c_i32]),
-    'stk_pcg_solve_slab': (ctypes.c_int, [
-        c_p, c_i32, c_i32, c_i32, c_i32, c_i32, OPERATOR_FN, c_p, OPERATOR_FN, c_p,
-        ALLREDUCE_FN, c_p, c_p, c_p, c_f64, c_i32, c_p, c_p, c_p
-    ]),
-    'stk_slab_dot_work_size': (c_i64, [c_i32, c_i32]),
-    'stk_slab_dot': (ctypes.c_int, [c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_p]),
-    'stk_sum_steps': (c_f64, [c_p, c_i32]),
-    'stk_slab_gather_columns': (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_i32]),
-    'stk_slab_scatter_columns': (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_i32]),
-    'stk_slab_ld': (ctypes.c_int, [c_i32]),
-    'stk_slab_alloc': (ctypes.c_int, [c_i32, c_i32, c_p, c_p]),
-    'stk_slab_free': (ctypes.c_int, [c_p]),
-    'stk_slab_upload': (ctypes.c_int, [c_p, c_i32, c_i32, c_i32, c_p, c_p]),
-    'stk_slab_download': (ctypes.c_int, [c_p, c_i32, c_i32, c_i32, c_p, c_p]),
-    'stk_transpose': (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_i64, c_p, c_i64, c_i32]),
-    'stk_halo_pack': (ctypes.c_int, [c_p, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_i32]),
-    'stk_slab_extract_time_rows': (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_i64]),
-    'stk_copy_block': (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_i64, c_p, c_i64]),
-    'stk_outer': (ctypes.c_int, [c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
-    'stk_comm_unique_id': (ctypes.c_int, [c_p]),
-    'stk_comm_create': (ctypes.c_int, [c_i32, c_i32, c_p, ctypes.POINTER(c_p)]),
-    'stk_comm_destroy': (ctypes.c_int, [c_p]),
-    'stk_comm_allreduce_sum': (ctypes.c_int, [c_p, c_p, c_p, c_i32]),
-    'stk_comm_halo_exchange': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p, c_p, c_p]),
-    'stk_comm_exchange': (ctypes.c_int, [c_p, c_p, c_i32, ctypes.POINTER(CommMsg), c_i32,
-                                         ctypes.POINTER(CommMsg)]),
-    'stk_ell_from_csr': (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_p,
-                                        c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
-    'stk_gs_depth_step': (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p]),
-    'stk_csr_galerkin': (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                        c_i32, c_p, c_p, c_p, c_p]),
-    'stk_timing_enable': (ctypes.c_int, [c_i32]),
-    'stk_timing_reset': (ctypes.c_int, []),
-    'stk_timing_get': (ctypes.c_int, [ctypes.c_char_p, c_p, c_p]),
-    'stk_lanczos_work_size': (c_i64, [c_i64]),
-    'stk_lanczos': (ctypes.c_int, [
-        c_p, c_i64, OPERATOR_FN, c_p, OPERATOR_FN, c_p, ALLREDUCE_FN, c_p, c_p,
-        c_i32, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p
-    ]),
-    'stk_mg_coarse_levels': (ctypes.c_int, [c_p]),
-    'stk_mg_set_member_matrices': (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_p, c_p]),
-    'stk_lu_create': (ctypes.c_int, [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p)]),
-    'stk_lu_destroy': (ctypes.c_int, [c_p]),
-    'stk_lu_info': (ctypes.c_int, [c_p, c_p, c_p, c_p]),
-    'stk_lu_top_rows': (ctypes.c_int, [c_p, c_p, c_p]),
-    'stk_lu_set_top_inverse': (ctypes.c_int, [c_p, c_p, c_p, c_i32]),
-    'stk_lu_solve': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_p, c_p, c_p]),
-    'stk_lanczos_slab_work_size': (c_i64, [c_i32, c_i32, c_i32, c_i32]),
-    'stk_lanczos_slab': (ctypes.c_int, [
-        c_p, c_i32, c_i32, c_i32, c_i32, c_i32, OPERATOR_FN, c_p, OPERATOR_FN, c_p,
-        ALLREDUCE_FN, c_p, c_p, c_i32, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p
-    ]),
-    'stk_kron_ell_apply': (ctypes.c_int, [
-        c_p, ctypes.POINTER(EllPattern), c_i32, c_i32, c_i32,
-        ctypes.POINTER(KronEllTerm), c_f64, c_p
-    ]),
-    'stk_kron_ell_ghost_apply': (ctypes.c_int, [
-        c_p, ctypes.POINTER(EllPattern), c_i32, c_i32, c_i32,
-        ctypes.POINTER(KronEllTerm), c_p
-    ]),
-    'stk_pack_unit_slots': (c_i32, [c_i32, c_i32]),
-    'stk_pack_match_order': (ctypes.c_int, [c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_p]),
-    'stk_pack_group_rows': (ctypes.c_int, [
-        c_i32, c_i32, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p
-    ]),
-    'stk_kron_pack_apply': (ctypes.c_int, [
-        c_p, ctypes.POINTER(PackPattern), c_i32, c_i32, c_i32,
-        ctypes.POINTER(KronPackTerm), c_p, c_p, c_f64, c_p
-    ]),
-    'stk_kron_pack_ghost_apply': (ctypes.c_int, [
-        c_p, ctypes.POINTER(PackPattern), c_i32, c_i32, c_i32,
-        ctypes.POINTER(KronPackTerm), c_p, c_p, c_p, c_p
-    ]),
-    'stk_kron_plan_boundary_apply': (ctypes.c_int, [
-        c_p, c_p, c_i32, c_i32, c_i32, ctypes.POINTER(KronPackTerm), c_p, c_p, c_p, c_p, c_p, c_p
-    ]),
-    'stk_kron_pack_boundary_apply': (ctypes.c_int, [
-        c_p, ctypes.POINTER(PackPattern), c_i32, c_i32, c_i32,
-        ctypes.POINTER(KronPackTerm), c_p, c_p, c_i32, c_i32, c_p
-    ]),
-    'stk_halo_pack_records': (ctypes.c_int, [c_p, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_i32, c_p]),
-    'stk_kron_pack_apply_multi': (ctypes.c_int, [
-        c_p, ctypes.POINTER(PackPattern), c_i32, c_i32, c_i32,
-        ctypes.POINTER(KronPackTerm), ctypes.POINTER(c_p), c_f64, c_p
-    ]),
-    'stk_kron_pack_apply_multi_steps': (ctypes.c_int, [
-        c_p, ctypes.POINTER(PackPattern), c_i32, c_i32, c_i32,
-        ctypes.POINTER(KronPackTerm), ctypes.POINTER(c_p), c_p, c_p, c_f64, c_p
-    ]),
-    'stk_mg_set_coarse_inverse': (ctypes.c_int, [c_p, c_p]),
-    'stk_interleave_ghosts': (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_p]),
-    'stk_kron_plan_create': (ctypes.c_int, [
-        c_i32, c_i32, ctypes.POINTER(c_p), ctypes.POINTER(c_p),
-        ctypes.POINTER(c_p), c_p, ctypes.POINTER(c_p)
-    ]),
-    'stk_kron_plan_destroy': (ctypes.c_int, [c_p]),
-    'stk_kron_plan_info': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p]),
-    'stk_kron_plan_apply': (ctypes.c_int, [
-        c_p, c_p, c_i32, c_i32, c_i32, ctypes.POINTER(KronPackTerm), c_p, c_p,
-        c_p, c_p, c_f64, c_p
-    ]),
-    'stk_kron_plan_ghost_apply': (ctypes.c_int, [
-        c_p, c_p, c_i32, c_i32, c_i32, ctypes.POINTER(KronPackTerm), c_p, c_p,
-        c_p, c_p
-    ]),
-    'stk_ell_spmm': (ctypes.c_int, [
-        c_p, ctypes.POINTER(EllRows), c_i32, c_i32, c_i32, c_f64, c_p, c_p,
-        c_f64, c_f64, c_p, c_p
-    ]),
-    'stk_csr_spmm': (ctypes.c_int, [
-        c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_f64, c_p, c_p, c_p, c_f64,
-        c_f64, c_p, c_p
-    ]),
-    'stk_time_csr_apply': (ctypes.c_int, [
-        c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_p
-    ]),
-    'stk_time_dense_apply': (ctypes.c_int, [
-        c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p
-    ]),
-    'stk_elem_time_apply': (ctypes.c_int, [
-        c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_p), ctypes.POINTER(c_p),
-        ctypes.POINTER(c_p), c_f64, c_p
-    ]),
-    'stk_elem_time_apply_t': (ctypes.c_int, [
-        c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_f64, c_p
-    ]),
-    'stk_kron_pack_elem_lds_bytes': (c_i64, [ctypes.POINTER(PackPattern), c_i32, c_i32, c_i32]),
-    'stk_kron_pack_elem_apply': (ctypes.c_int, [
-        c_p, ctypes.POINTER(PackPattern), c_i32, c_i32, c_i32, c_i32, c_i32,
-        ctypes.POINTER(KronPackTerm), ctypes.POINTER(c_p), c_p, c_p, c_f64, c_p
-    ]),
-    'stk_kron_pack_elem_apply_t': (ctypes.c_int, [
-        c_p, ctypes.POINTER(PackPattern), c_i32, c_i32, c_i32, c_i32, c_i32,
-        ctypes.POINTER(KronPackTerm), ctypes.POINTER(c_p), c_p, c_f64, c_p
-    ]),
-    'stk_elem_block_mix': (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_p, c_p]),
-    'stk_wavelet_apply': (ctypes.c_int,
-                          [c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
-    'stk_mg_create': (ctypes.c_int, [
-        c_i32,
-        ctypes.POINTER(MGLevel), c_i32, c_i32, c_i32, c_p, c_i32,
-        ctypes.POINTER(c_p)
-    ]),
-    'stk_mg_create_from_csr': (ctypes.c_int, [
-        c_i32, ctypes.POINTER(CsrHost), ctypes.POINTER(CsrHost),
-        ctypes.POINTER(CsrHost), c_p, c_i32, c_i32, c_i32, c_f64, c_i32, c_p,
-        c_i32, ctypes.POINTER(c_p)
-    ]),
-    'stk_p1_assemble_2d': (ctypes.c_int, [c_i64, c_i64, c_p, c_p, c_p, c_f64, ctypes.POINTER(c_p)]),
-    'stk_p1_result_sizes': (ctypes.c_int, [c_p, c_p, c_p, c_p]),
-    'stk_p1_result_copy': (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_p]),
-    'stk_p1_result_free': (ctypes.c_int, [c_p]),
-    'stk_p1_load_points_2d': (ctypes.c_int, [c_i64, c_i64, c_p, c_p, c_i32, c_p, c_p, c_p]),
-    'stk_p1_load_sum_2d': (ctypes.c_int, [c_i64, c_i64, c_p, c_p, c_i32, c_p, c_p, c_p, c_p]),
-    'stk_load_plan_create': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_i32,
-                                            ctypes.POINTER(c_p)]),
-    'stk_load_plan_destroy': (ctypes.c_int, [c_p]),
-    'stk_load_points': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p]),
-    'stk_load_columns': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_i32, c_i32, c_p]),
-    'stk_sample_grid_build': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, ctypes.POINTER(c_p)]),
-    'stk_sample_grid_sizes': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p]),
-    'stk_sample_grid_copy': (ctypes.c_int, [c_p, c_p, c_p]),
-    'stk_sample_grid_free': (ctypes.c_int, [c_p]),
-    'stk_sample_plan_create': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_i64, c_p, ctypes.POINTER(c_p)]),
-    'stk_sample_plan_destroy': (ctypes.c_int, [c_p]),
-    'stk_sample_locate': (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_p]),
-    'stk_sample_eval': (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_i32, c_p, c_p,
-                                       c_i64, c_p]),
-    'stk_sample_pairs': (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_p, c_f64, c_i32, c_i32, c_i32, c_i32, c_i32, c_p,
-                                        c_i32, c_i64, c_p]),
-    'stk_sample_grad_coeffs': (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p]),
-    'stk_sample_pairs_adjoint_work_size': (ctypes.c_int, [c_i64, c_i32, c_p]),
-    'stk_sample_pairs_adjoint': (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_p, c_f64, c_i32, c_i32, c_i32, c_i32, c_i32,
-                                                c_p, c_p, c_i64, c_i32, c_i32, c_p, c_p, c_i64]),
-    'stk_err_plan_create': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_i64, c_p, ctypes.POINTER(c_p)]),
-    'stk_err_plan_destroy': (ctypes.c_int, [c_p]),
-    'stk_err_points': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p]),
-    'stk_err_element': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p,
-                                       c_i64, c_p]),
-    'stk_history_scan': (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_i64, c_i64, c_i64, c_f64, c_f64, c_i32, c_p]),
-    'stk_history_tile': (ctypes.c_int, [c_i32, c_i32]),
-    'stk_curves_rows': (ctypes.c_int, [c_i32]),
-    'stk_curves_boundary_faces': (ctypes.c_int, [c_i32, c_i64, c_p, c_p]),
-    'stk_curves_plan_create': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_i64, c_p, ctypes.POINTER(c_p)]),
-    'stk_curves_plan_destroy': (ctypes.c_int, [c_p]),
-    'stk_curves_eval': (ctypes.c_int, [c_p, c_p, c_i64, c_i32, c_p, c_i64, c_f64, c_i64, c_p]),
-    'stk_curves_tile': (ctypes.c_int, [c_i32]),
-    'stk_curves_batch': (ctypes.c_int, [c_i64]),
-    'stk_iso_width': (ctypes.c_int, [c_i32]),
-    'stk_iso_count': (ctypes.c_int, [c_p, c_p, c_i64, c_i32, c_p, c_i64, c_f64, c_p]),
-    'stk_iso_fill': (ctypes.c_int, [c_p, c_p, c_i64, c_i32, c_p, c_i64, c_f64, c_p, c_p, c_i64, c_p]),
-    'stk_iso_tile': (ctypes.c_int, [c_i32]),
-    'stk_solid_rows': (ctypes.c_int, [c_i32]),
-    'stk_solid_tile_rows': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
-    'stk_solid_plan_create': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_i64, c_p, ctypes.POINTER(c_p)]),
-    'stk_solid_plan_destroy': (ctypes.c_int, [c_p]),
-    'stk_solid_scan': (ctypes.c_int, [c_p, c_p, c_i64, c_i32, c_p, c_i64, c_i64, c_f64, c_f64, c_i32, c_p]),
-    'stk_solid_tile': (ctypes.c_int, [c_i32, c_i32]),
-    'stk_solid_cell_order': (ctypes.c_int, [c_i32, c_i64, c_i64, c_p, c_p, c_p]),
-    'stk_solid_order': (ctypes.c_int, [c_i32]),
-    'stk_transfer_plan_create': (ctypes.c_int, [c_i64, c_i64, c_p, ctypes.POINTER(c_p)]),
-    'stk_transfer_plan_destroy': (ctypes.c_int, [c_p]),
-    'stk_transfer_tile': (ctypes.c_int, [c_i32, c_i32]),
-    'stk_transfer_prolong': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i64, c_i32]),
-    'stk_tile_order': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_f64, c_p]),
-    'stk_csr_union_count': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_p]),
-    'stk_csr_union_fill': (ctypes.c_int, [c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
-    'stk_tri_refine': (ctypes.c_int, [c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
-    'stk_mg_destroy': (ctypes.c_int, [c_p]),
-    'stk_mg_set_option': (ctypes.c_int, [c_p, ctypes.c_char_p, c_i32]),
-    'stk_mg_apply': (ctypes.c_int,
-                     [c_p, c_p, c_i32, c_i32, c_f64, c_p, c_p, c_p, c_p]),
-    'stk_mg_smooth': (ctypes.c_int, [
-        c_p, c_p, c_i32, c_i32, c_i32, c_f64, c_p, c_i32, c_i32, c_p, c_p
-    ]),
-}
-
-EXPORTED_SYMBOLS = sorted(_PROTOTYPES)
-
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), 'include', 'stk.h')
 
 
 class StkError(RuntimeError):
     pass
+
+
+# callbacks of stk_pcg_solve (include/stk.h); how a callback receives its arguments is this side's choice
+OPERATOR_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)
+ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int32)
+CALLBACKS = {'stk_operator_fn': OPERATOR_FN, 'stk_allreduce_fn': ALLREDUCE_FN}
+
+# the header's structs under the names the package uses
+STRUCT_NAMES = {'stk_ell_pattern': 'EllPattern', 'stk_kron_ell_term': 'KronEllTerm', 'stk_pack_pattern': 'PackPattern',
+                'stk_kron_pack_term': 'KronPackTerm', 'stk_comm_msg': 'CommMsg', 'stk_ell_rows': 'EllRows',
+                'stk_csr_host': 'CsrHost', 'stk_mg_level': 'MGLevel'}
+
+_SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'double': ctypes.c_double}
+
+
+def bind(text):
+    """The binding that header text states, as _header.parse reads it: (struct classes by C name,
+    {function: (restype, argtypes)}, constants).  include/stk.h is the only statement of the ABI."""
+    header = _header.parse(text)
+    structs = {}
+
+    def ctype(t):
+        if t.stars == 0:
+            return CALLBACKS.get(t.base, ctypes.c_void_p) if t.base in header.callbacks else _SCALARS[t.base]
+        if t.stars == 1 and t.base == 'char' and t.const[0]:
+            return ctypes.c_char_p
+        if t.stars == 1 and t.base in structs:
+            return ctypes.POINTER(structs[t.base])
+        if t.stars == 2 and t.base in header.handles:  # the out-parameter of a *_create
+            return ctypes.POINTER(ctypes.c_void_p)
+        return ctypes.c_void_p
+
+    for name, fields in header.structs:
+        structs[name] = type(STRUCT_NAMES.get(name, name), (ctypes.Structure,),
+                             {'_fields_': [(f, ctype(t)) for f, t in fields]})
+    prototypes = {f.name: (ctype(f.ret), [ctype(p.type) for p in f.params]) for f in header.functions}
+    return structs, prototypes, header.constants
+
+
+def _bind_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return bind(f.read())
+    except (OSError, _header.HeaderError) as e:
+        raise StkError('cannot bind libstk from %s: %s' % (HEADER_PATH, e)) from e
+
+
+_structs, prototypes, _constants = _bind_header()
+globals().update({cls.__name__: cls for cls in _structs.values()})  # EllPattern, ..., MGLevel
+globals().update(_constants)  # STK_TRANSFER_MAX_A, ...
+EXPORTED_SYMBOLS = sorted(prototypes)
+
+_lib = None
 
 
 def lib():
@@ -335,7 +86,7 @@ def lib():
                 '`make -C spacetime-fullgrid-parallel_amd/csrc`. '
                 'There is no CPU fallback.' % LIB_PATH)
         _lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOTYPES.items():
+        for name, (res, args) in prototypes.items():
             fn = getattr(_lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -609,7 +609,7 @@ class ElementKronMatMPI(LinearOperatorMPI):
         this order, where the caller holds it (the driver: the plan S streams; None: the
         shared plan of these matrices, built if nobody holds it any more)."""
         super().__init__(dofs_distr)
-        assert 1 <= len(blocks_per_term) == len(mats_space) <= 3
+        assert 1 <= len(blocks_per_term) == len(mats_space) <= _lib.STK_ELEM_MAX_TERMS
         self.dofs_test = ElementDistributionMPI(dofs_distr)
         self.transposed = bool(transposed)
         dt = self.dofs_test

@@ -41,9 +41,12 @@ def n_rows(d):
 
 def rows(d):
     """{name: row or slice of rows} of the (stk_solid_rows(d), nc) state: the indices of
-    include/stk.h."""
-    return {'t_solid': 0, 'cooling_rate': 1, 'n_solid': 2, 'max_grad_sq': 3, 't_max_grad': 4, 'last_mean': 5,
-            'grad_solid': slice(6, 6 + d), 'last_grad': slice(6 + d, 6 + 2 * d)}
+    include/stk.h (STK_SOLID_*)."""
+    from . import _lib as c
+    g = c.STK_SOLID_GRAD_SOLID
+    return {'t_solid': c.STK_SOLID_T_SOLID, 'cooling_rate': c.STK_SOLID_COOLING_RATE, 'n_solid': c.STK_SOLID_N_SOLID,
+            'max_grad_sq': c.STK_SOLID_MAX_GRAD_SQ, 't_max_grad': c.STK_SOLID_T_MAX_GRAD,
+            'last_mean': c.STK_SOLID_LAST_MEAN, 'grad_solid': slice(g, g + d), 'last_grad': slice(g + d, g + 2 * d)}
 
 
 def check_arguments(threshold, points=None, d=None, fields=None):

@@ -33,9 +33,13 @@ FIELDS = ALWAYS + THRESHOLD_FIELDS
 
 def rows(d):
     """{name: row or slice of rows} of the (stk_curves_rows(d), n) output: the indices of
-    include/stk.h."""
-    return {'heat': 0, 'l2_sq': 1, 'h1_sq': 2, 'outflow': 3, 'measure_above': 4, 'moment_above': slice(5, 5 + d),
-            'peak': 5 + d, 'peak_row': 6 + d, 'box_lo': slice(7 + d, 7 + 2 * d), 'box_hi': slice(7 + 2 * d, 7 + 3 * d)}
+    include/stk.h (STK_CURVES_*; the rows behind the moment as its function-like macros count them)."""
+    from . import _lib as c
+    m = c.STK_CURVES_MOMENT
+    return {'heat': c.STK_CURVES_HEAT, 'l2_sq': c.STK_CURVES_L2, 'h1_sq': c.STK_CURVES_H1,
+            'outflow': c.STK_CURVES_OUTFLOW, 'measure_above': c.STK_CURVES_MEASURE, 'moment_above': slice(m, m + d),
+            'peak': m + d, 'peak_row': m + 1 + d, 'box_lo': slice(m + 2 + d, m + 2 + 2 * d),
+            'box_hi': slice(m + 2 + 2 * d, m + 2 + 3 * d)}
 
 
 def n_rows(d):

@@ -26,7 +26,9 @@ import ctypes
 
 import numpy as np
 
-MAX_A = 8  # STK_TRANSFER_MAX_A
+from . import _lib
+
+MAX_A = _lib.STK_TRANSFER_MAX_A
 
 
 def parent_rows(mesh, level=None):
@@ -102,7 +104,6 @@ class _PlanHandle:
     def __init__(self, table, M_coarse):
         import torch
 
-        from . import _lib
         table = np.ascontiguousarray(table, dtype=np.int32)
         assert table.ndim == 2 and table.shape[1] == 2, table.shape
         self.M_fine, self.M_coarse = len(table), int(M_coarse)
@@ -144,7 +145,6 @@ def prolong_scan(plan, a, uc, ldc, qc_first, n_cc, out, ld, k_first, n_cols):
     columns [k_first, k_first + n_cols) into out[i * ld + c] from the coarse columns
     [qc_first, qc_first + n_cc) at uc[j * ldc + (q - qc_first)]; `uc`, `out`: device tensors
     or device addresses."""
-    from . import _lib
     from .p1_plan import device_address
     _lib.check(_lib.lib().stk_transfer_prolong(_lib.stream(), plan, int(a), device_address(uc), int(ldc), int(qc_first),
                                                int(n_cc), device_address(out), int(ld), int(k_first), int(n_cols)))
@@ -179,7 +179,6 @@ def prolong_collective(plan, coarse_vec, fine_distr):
     launch, so the doubles are the one-rank doubles whatever the number of ranks."""
     import torch
 
-    from . import _lib
     from .mpi_vector import KronVectorMPI
     cd = coarse_vec.dofs_distr
     if (coarse_vec.N, coarse_vec.M) != (plan.N_coarse, plan.M_coarse):

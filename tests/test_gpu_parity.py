@@ -1622,7 +1622,6 @@ def test_slab_dot_does_not_depend_on_the_partition(stk):
                 total += part  # what the all-reduce does: every entry has one contributor
             assert np.array_equal(total, whole), (M, N, size)
         host = np.ascontiguousarray(whole)
-        lib.stk_sum_steps.restype = ctypes.c_double
         s = 0.0
         for v in whole:
             s += v

@@ -43,9 +43,9 @@ UNCALLED_EXPORTS = set()
 
 def test_every_declared_function_is_called_somewhere():
     """Every function of include/stk.h is called by name -- `stk_x(` -- in the suite
-    (Python and the C hosts under tests/), in the package's Python outside _lib.py's
-    prototype table, or in bench.py: the next export that nothing exercises fails
-    here instead of waiting for a review."""
+    (Python and the C hosts under tests/), in the package's Python, or in bench.py:
+    the next export that nothing exercises fails here instead of waiting for a
+    review."""
     header = open(os.path.join(REPO, 'include', 'stk.h')).read()
     declared = set(re.findall(r'\b(stk_[a-z0-9_]+)\s*\(', header)) - {'stk_mg'}
     texts = [open(os.path.join(REPO, 'bench.py')).read()]
@@ -54,11 +54,7 @@ def test_every_declared_function_is_called_somewhere():
             for f in files:
                 if not f.endswith(('.py', '.c', '.cpp')):
                     continue
-                text = open(os.path.join(dirpath, f)).read()
-                if f == '_lib.py':
-                    text, n = re.subn(r'\n_PROTOTYPES = \{\n.*?\n\}\n', '\n', text, flags=re.S)
-                    assert n == 1, 'the prototype table of _lib.py was not found'
-                texts.append(text)
+                texts.append(open(os.path.join(dirpath, f)).read())
     called = set(re.findall(r'\b(stk_[a-z0-9_]+)\s*\(', '\n'.join(texts)))
     assert not UNCALLED_EXPORTS, 'keep the allow-list empty: call %s' % sorted(UNCALLED_EXPORTS)
     missing = sorted(declared - called - UNCALLED_EXPORTS)
@@ -728,7 +724,6 @@ def test_host_side_of_the_partition_independent_dot():
     import ctypes
     from source import _lib
     lib = _lib.lib()
-    lib.stk_sum_steps.restype = ctypes.c_double
     rng = np.random.RandomState(6)
     for N in (1, 2, 9, 65, 129, 300):
         steps = np.ascontiguousarray(rng.randn(N) * 10.0**rng.randint(-8, 8, size=N))
