@@ -21,6 +21,25 @@ extern "C" const char *stk_last_error(void) { return g_err; }
 
 extern "C" int stk_version(void) { return 200; }
 
+// ---- the seam of dev_arrays.h: every plan's device arrays come and go through here ----
+void *stk_dev_malloc(size_t bytes)
+{
+    void *p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) return p;
+    stk_set_error("hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    return nullptr;
+}
+
+void stk_dev_free(void *p) { (void)hipFree(p); }
+
+bool stk_dev_copy_in(void *dst, const void *src, size_t bytes)
+{
+    const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) stk_set_error("hipMemcpy of %zu bytes to the device failed: %s", bytes, hipGetErrorString(e));
+    return e == hipSuccess;
+}
+
 // ---- tuning keys (stk.h documents each one) ------------------------------------
 stk_tuning g_tuning;
 

@@ -373,14 +373,6 @@ __global__ __launch_bounds__(BS) void curves_finish_kernel(int64_t n_tiles, int6
     (void)R;
 }
 
-void release(stk_curves_plan *p)
-{
-    if (!p) return;
-    p1_mesh_free(&p->mesh);
-    p1_free({p->vol, p->grad, p->faces, p->work});
-    delete p;
-}
-
 struct face_key {
     int32_t v[3];  // the face's vertices, ascending; -1 in the last place of an edge
     int32_t slot;  // (d + 1) cell + a
@@ -451,12 +443,12 @@ extern "C" int stk_curves_plan_create(int32_t d, int64_t nv, int64_t nc, const d
     p->n_work = p->n_tiles > row_tiles ? p->n_tiles : row_tiles;  // (below 2^23 by the checks above: one grid takes it)
     const int64_t one_column = (int64_t)n_rows(d) * p->n_work;
     p->work_doubles = std::max(one_column, BATCH_BYTES / 8);
-    int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, cells, &row_of);
-    if (!rc) rc = p1_upload(&p->faces, faces.data(), faces.size());
-    if (!rc) rc = p1_geometry(who, p, &p->vol);
-    if (!rc) rc = p1_hip(who, hipMalloc((void **)&p->work, (size_t)p->work_doubles * sizeof(double)));
+    int rc = p1_mesh_upload(p->dev, &p->mesh, d, nv, nc, points, cells, &row_of);
+    if (!rc) rc = !(p->faces = p->dev.upload(faces));
+    if (!rc) rc = p1_geometry(who, p->dev, p, &p->vol);
+    if (!rc && !(p->work = p->dev.alloc<double>((size_t)p->work_doubles))) rc = p1_no_array(who);
     if (rc) {
-        release(p);
+        delete p;
         return rc;
     }
     *out = p;
@@ -465,7 +457,7 @@ extern "C" int stk_curves_plan_create(int32_t d, int64_t nv, int64_t nc, const d
 
 extern "C" int stk_curves_plan_destroy(stk_curves_plan *plan)
 {
-    release(plan);
+    delete plan;
     return 0;
 }
 

@@ -19,6 +19,7 @@ struct stk_curves_plan {
     uint8_t *faces;  // [nc]: bit a = the face opposite vertex a is a boundary face
     double *work;    // [rows][batch columns][n_work] partials of a batch in flight
     int64_t work_doubles;
+    stk_dev_arrays dev;  // owns every device array above
 };
 
 namespace {

@@ -35,6 +35,7 @@ struct stk_err_plan {
     double *vol;   // [nc]
     double *grad;  // [nc][d + 1][d]
     double *work;  // [n_tiles][4] partials of a call in flight
+    stk_dev_arrays dev;  // owns every device array above
 };
 
 namespace {
@@ -183,14 +184,6 @@ __global__ __launch_bounds__(BS) void err_finish_kernel(int64_t n_tiles, int64_t
     if (tid < 4) out4[tid] = red[tid * BS];
 }
 
-void release(stk_err_plan *p)
-{
-    if (!p) return;
-    p1_mesh_free(&p->mesh);
-    p1_free({p->vol, p->grad, p->work});
-    delete p;
-}
-
 }  // namespace
 
 extern "C" int stk_err_plan_create(int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells,
@@ -202,11 +195,11 @@ extern "C" int stk_err_plan_create(int32_t d, int64_t nv, int64_t nc, const doub
 
     stk_err_plan *p = new stk_err_plan();
     p->d = d, p->nv = nv, p->nc = nc, p->n_free = n_free, p->n_tiles = (nc + BS - 1) / BS;
-    int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, cells, &row_of);
-    if (!rc) rc = p1_geometry(who, p, &p->vol);
-    if (!rc) rc = p1_hip(who, hipMalloc((void **)&p->work, (size_t)p->n_tiles * 4 * sizeof(double)));
+    int rc = p1_mesh_upload(p->dev, &p->mesh, d, nv, nc, points, cells, &row_of);
+    if (!rc) rc = p1_geometry(who, p->dev, p, &p->vol);
+    if (!rc && !(p->work = p->dev.alloc<double>((size_t)p->n_tiles * 4))) rc = p1_no_array(who);
     if (rc) {
-        release(p);
+        delete p;
         return rc;
     }
     *out = p;
@@ -215,7 +208,7 @@ extern "C" int stk_err_plan_create(int32_t d, int64_t nv, int64_t nc, const doub
 
 extern "C" int stk_err_plan_destroy(stk_err_plan *plan)
 {
-    release(plan);
+    delete plan;
     return 0;
 }
 

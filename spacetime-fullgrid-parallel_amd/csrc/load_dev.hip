@@ -37,6 +37,7 @@ struct stk_load_plan {
     int32_t *inc_slot;           // slots of free dof i: inc_ptr[i] .. inc_ptr[i + 1], ascending
     int32_t *order;              // processing order of the free dofs, or null
     double *shares;              // [max_k][ns] workspace of stk_load_columns
+    stk_dev_arrays dev;          // owns every device array above
 };
 
 namespace {
@@ -129,14 +130,6 @@ __global__ __launch_bounds__(BS) void load_gather_kernel(int64_t n_free, int64_t
     }
 }
 
-void release(stk_load_plan *p)
-{
-    if (!p) return;
-    p1_mesh_free(&p->mesh);
-    p1_free({p->vol, p->inc_ptr, p->inc_slot, p->order, p->shares});
-    delete p;
-}
-
 }  // namespace
 
 extern "C" int stk_load_plan_create(int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells,
@@ -185,29 +178,27 @@ extern "C" int stk_load_plan_create(int32_t d, int64_t nv, int64_t nc, const dou
 
     stk_load_plan *p = new stk_load_plan();
     p->d = d, p->max_k = max_k, p->nv = nv, p->nc = nc, p->n_free = n_free, p->ns = ns;
-    int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, cells, nullptr);
-    if (!rc) rc = p1_upload(&p->inc_ptr, inc_ptr.data(), inc_ptr.size());
-    if (!rc) rc = p1_upload(&p->inc_slot, inc_slot.data(), inc_slot.size());
-    if (!rc && row_order) rc = p1_upload(&p->order, order.data(), order.size());
-    if (rc) {
-        release(p);
-        return rc;
+    int rc = p1_mesh_upload(p->dev, &p->mesh, d, nv, nc, points, cells, nullptr);
+    if (!rc) rc = !(p->inc_ptr = p->dev.upload(inc_ptr)) || !(p->inc_slot = p->dev.upload(inc_slot));
+    if (!rc && row_order) rc = !(p->order = p->dev.upload(order));
+    if (!rc) {
+        p->vol = p->dev.alloc<double>((size_t)nc);
+        p->shares = p->vol ? p->dev.alloc<double>((size_t)max_k * ns) : nullptr;
+        if (!p->shares) rc = p1_no_array("stk_load_plan_create");
     }
-    hipError_t e = hipMalloc((void **)&p->vol, (size_t)nc * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->shares, (size_t)max_k * ns * sizeof(double));
-    if (e == hipSuccess) {
+    if (!rc) {
         const dim3 grid(stk_flat_grid(nc, BS));
         if (d == 2)
             hipLaunchKernelGGL(load_volume_kernel<2>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol);
         else
             hipLaunchKernelGGL(load_volume_kernel<3>, grid, dim3(BS), 0, 0, nc, p->mesh.points, p->mesh.cells, p->vol);
-        e = hipGetLastError();
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        rc = p1_hip("stk_load_plan_create", e);
     }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        stk_set_error("stk_load_plan_create: %s", hipGetErrorString(e));
-        release(p);
-        return 1;
+    if (rc) {
+        delete p;
+        return rc;
     }
     *out = p;
     return 0;
@@ -215,7 +206,7 @@ extern "C" int stk_load_plan_create(int32_t d, int64_t nv, int64_t nc, const dou
 
 extern "C" int stk_load_plan_destroy(stk_load_plan *plan)
 {
-    release(plan);
+    delete plan;
     return 0;
 }
 

@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <string>
 #include <vector>
 
 #include "csr_spmm.h"
@@ -126,8 +127,9 @@ struct stk_mg {
     // fused coarse sub-V-cycle: levels 0..Lc in one launch (Lc < 0: none)
     stk_coarse_plan *coarse = nullptr;
     int Lc = -1;
-    // device arrays the plan owns (plans built by stk_mg_create_from_csr)
-    std::vector<void *> adopted;
+    // device arrays the plan owns: the workspaces, and what stk_mg_create_from_csr built
+    stk_dev_arrays dev;
+    ~stk_mg() { stk_coarse_plan_free(coarse); }
     // -1: follow the process-wide tuning key "mg_fuse_restrict"; 0 / 1: this plan's
     // own choice (stk_mg_set_option; 0 is part of the reference-arithmetic mode)
     int fuse_restrict = -1;
@@ -447,16 +449,15 @@ extern "C" int stk_mg_create(int32_t n_levels, const stk_mg_level *levels, int32
             mg->fwd_ptr[j].assign(L.fwd_ptr_host, L.fwd_ptr_host + L.n_fwd + 1);
             mg->bwd_ptr[j].assign(L.bwd_ptr_host, L.bwd_ptr_host + L.n_bwd + 1);
         }
-        const size_t bytes = sizeof(double) * (size_t)L.n * max_ld;
-        hipError_t e = hipSuccess;
-        if (j < n_levels - 1) {
-            e = hipMalloc((void **)&mg->u[j], bytes);
-            if (e == hipSuccess) e = hipMalloc((void **)&mg->f[j], bytes);
-        }
-        if (e == hipSuccess && j > 0) e = hipMalloc((void **)&mg->r[j], bytes);
-        if (e != hipSuccess) {
-            stk_set_error("stk_mg_create: hipMalloc failed on level %d: %s", j, hipGetErrorString(e));
-            stk_mg_destroy(mg);
+        const size_t doubles = (size_t)L.n * max_ld;
+        bool ok = true;
+        if (j < n_levels - 1)
+            ok = (mg->u[j] = mg->dev.alloc<double>(doubles)) && (mg->f[j] = mg->dev.alloc<double>(doubles));
+        if (ok && j > 0) ok = (mg->r[j] = mg->dev.alloc<double>(doubles));
+        if (!ok) {
+            const std::string why = stk_last_error();
+            stk_set_error("stk_mg_create: level %d: %s", j, why.c_str());
+            delete mg;
             return 1;
         }
     }
@@ -521,19 +522,10 @@ extern "C" int stk_mg_set_member_matrices(stk_mg *mg, int32_t level, int32_t n_k
                                        data_host);
 }
 
-void stk_mg_adopt(stk_mg *mg, void *const *dev_ptrs, int n)
-{
-    mg->adopted.insert(mg->adopted.end(), dev_ptrs, dev_ptrs + n);
-}
+stk_dev_arrays &stk_mg_arrays(stk_mg *mg) { return mg->dev; }
 
 extern "C" int stk_mg_destroy(stk_mg *mg)
 {
-    if (!mg) return 0;
-    for (void *p : mg->adopted) (void)hipFree(p);
-    for (double *p : mg->u) (void)hipFree(p);
-    for (double *p : mg->f) (void)hipFree(p);
-    for (double *p : mg->r) (void)hipFree(p);
-    stk_coarse_plan_free(mg->coarse);
     delete mg;
     return 0;
 }

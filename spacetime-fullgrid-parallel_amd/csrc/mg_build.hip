@@ -329,7 +329,7 @@ std::vector<int32_t> coupling_bands(const double *coords, int dim, const Union &
 
 // ---- the builder -------------------------------------------------------------
 struct Builder {
-    std::vector<void *> dev;  // every device allocation (adopted by the plan)
+    stk_dev_arrays dev;  // every device allocation (taken by the plan)
     std::atomic<bool> failed{false};
     std::mutex mu;  // the pieces of a level are built by several host threads
 
@@ -340,16 +340,14 @@ struct Builder {
             std::vector<T> one(1, T());
             return up(one);
         }
-        T *d = nullptr;
-        if (hipMalloc((void **)&d, h.size() * sizeof(T)) != hipSuccess ||
-            hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+        stk_dev_arrays mine;  // the allocation and the copy run beside those of the other threads
+        const T *d = mine.upload(h);
+        if (!d) {
             failed = true;
             return nullptr;
         }
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            dev.push_back(d);
-        }
+        std::lock_guard<std::mutex> lock(mu);
+        dev.take(std::move(mine));
         return d;
     }
 };
@@ -772,10 +770,7 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
         int rc = build_level(J);
         chain.join();
         for (int j = J - 1; j >= 0 && rc == 0; --j) rc = build_level(j);
-        if (rc) {
-            for (void *d : B.dev) (void)hipFree(d);
-            return rc;
-        }
+        if (rc) return rc;
     }
     // ---- exact coarse inverses: kind 0 = A_0 alone, kind 1 + k = ca*A_0 + cms[k]*M_0 --
     const int n0 = A[0].rows;
@@ -798,17 +793,12 @@ extern "C" int stk_mg_create_from_csr(int32_t n_levels, const stk_csr_host *A_fi
     }
     const double *d_inv = B.up(inv);
     if (B.failed) {
-        for (void *d : B.dev) (void)hipFree(d);
         stk_set_error("stk_mg_create_from_csr: device allocation or copy failed");
         return 1;
     }
     stk_mg *mg = nullptr;
-    const int rc = stk_mg_create(n_levels, lv.data(), smoothsteps, vcycles, n_kinds, d_inv, max_ld, &mg);
-    if (rc) {
-        for (void *d : B.dev) (void)hipFree(d);
-        return rc;
-    }
-    stk_mg_adopt(mg, B.dev.data(), (int)B.dev.size());
+    if (int rc = stk_mg_create(n_levels, lv.data(), smoothsteps, vcycles, n_kinds, d_inv, max_ld, &mg)) return rc;
+    stk_mg_arrays(mg).take(std::move(B.dev));
     *out = mg;
     return 0;
 }

@@ -608,17 +608,10 @@ struct stk_coarse_plan {
     double *u_vmem = nullptr, *u_dmem = nullptr;  // [n_kinds][u_rows][KU], [n_kinds][u_rows]
     std::vector<char> member_level;  // [Lc + 1] members given for the level?
     bool members_ready = false;      // ... for all of 1..Lc
+    stk_dev_arrays dev;              // owns every device array above
 };
 
-void stk_coarse_plan_free(stk_coarse_plan *p)
-{
-    if (!p) return;
-    if (p->dev_jobs) (void)hipFree(p->dev_jobs);
-    for (void *q : {(void *)p->dev_cjobs, (void *)p->u_idx, (void *)p->u_row, (void *)p->u_va, (void *)p->u_vm,
-                    (void *)p->u_da, (void *)p->u_dm, (void *)p->u_level, (void *)p->u_vmem, (void *)p->u_dmem})
-        if (q) (void)hipFree(q);
-    delete p;
-}
+void stk_coarse_plan_free(stk_coarse_plan *p) { delete p; }
 
 static Job rows_job(int kind, const stk_ell_rows &e, int pos_begin, int pos_end, const double *x, const double *z,
                     double *y, double alpha, double beta, bool level_matrix, int level)
@@ -692,18 +685,11 @@ static void build_uniform(stk_coarse_plan *p)
     for (size_t n = 0; n < J.size(); ++n)
         if ((J[n].kind == JOB_SPMM || J[n].kind == JOB_GS) && J[n].use_m)
             for (int r = 0; r < cj[n].n_rows; ++r) row_level[cj[n].mat_off + r] = J[n].level;
-    bool ok = hipMalloc((void **)&p->u_level, sizeof(int32_t) * (size_t)total) == hipSuccess &&
-              hipMemcpy(p->u_level, row_level.data(), sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice) ==
-                  hipSuccess &&
-              hipMalloc((void **)&p->u_idx, sizeof(int32_t) * (size_t)total * KU) == hipSuccess &&
-              hipMalloc((void **)&p->u_va, sizeof(double) * (size_t)total * KU) == hipSuccess &&
-              hipMalloc((void **)&p->u_da, sizeof(double) * (size_t)total) == hipSuccess &&
-              hipMalloc((void **)&p->u_row, sizeof(int32_t) * (size_t)total) == hipSuccess &&
-              hipMalloc((void **)&p->dev_cjobs, sizeof(CJob) * cj.size()) == hipSuccess;
-    if (ok && has_m)
-        ok = hipMalloc((void **)&p->u_vm, sizeof(double) * (size_t)total * KU) == hipSuccess &&
-             hipMalloc((void **)&p->u_dm, sizeof(double) * (size_t)total) == hipSuccess;
-    if (ok) ok = hipMemcpy(p->dev_cjobs, cj.data(), sizeof(CJob) * cj.size(), hipMemcpyHostToDevice) == hipSuccess;
+    stk_dev_arrays &dev = p->dev;
+    bool ok = (p->u_level = dev.upload(row_level)) && (p->u_idx = dev.alloc<int32_t>((size_t)total * KU)) &&
+              (p->u_va = dev.alloc<double>((size_t)total * KU)) && (p->u_da = dev.alloc<double>(total)) &&
+              (p->u_row = dev.alloc<int32_t>(total)) && (p->dev_cjobs = dev.upload(cj));
+    if (ok && has_m) ok = (p->u_vm = dev.alloc<double>((size_t)total * KU)) && (p->u_dm = dev.alloc<double>(total));
     if (ok) {
         std::map<std::tuple<const int32_t *, int, int>, bool> done;
         for (const Job &j : J) {
@@ -800,29 +786,29 @@ int stk_coarse_plan_set_members(stk_coarse_plan *p, int level, int n_kinds, int3
                     n_missing, level);
     }
     if (p->u_vmem == nullptr) {
+        // the four fields of the first call are set together, once nothing can fail any more
         const size_t nv = (size_t)n_kinds * p->u_rows * p->KU, nd = (size_t)n_kinds * p->u_rows;
-        STK_HIP(hipMalloc((void **)&p->u_vmem, sizeof(double) * nv));
-        STK_HIP(hipMalloc((void **)&p->u_dmem, sizeof(double) * nd));
-        STK_HIP(hipMemset(p->u_vmem, 0, sizeof(double) * nv));
-        STK_HIP(hipMemset(p->u_dmem, 0, sizeof(double) * nd));
-        p->n_kinds = n_kinds;
+        stk_dev_arrays fresh;
+        double *vmem = fresh.alloc<double>(nv), *dmem = vmem ? fresh.alloc<double>(nd) : nullptr;
+        if (!dmem) return 1;
+        STK_HIP(hipMemset(vmem, 0, sizeof(double) * nv));
+        STK_HIP(hipMemset(dmem, 0, sizeof(double) * nd));
         p->member_level.assign(p->Lc + 1, 0);
+        p->dev.take(std::move(fresh));
+        p->u_vmem = vmem, p->u_dmem = dmem, p->n_kinds = n_kinds;
     }
-    int32_t *missing = nullptr;
-    STK_HIP(hipMalloc((void **)&missing, sizeof(int32_t)));
+    stk_dev_arrays temporaries;
+    int32_t *missing = temporaries.alloc<int32_t>(1);
+    if (!missing) return 1;
     STK_HIP(hipMemset(missing, 0, sizeof(int32_t)));
     int rc = 0;
     for (int k = 0; k < n_kinds && rc == 0; ++k) {
         if (indptr[k] == nullptr) continue;  // a kind no time slice names (the family's kind 0)
-        const int64_t nnz = indptr[k][n];
-        int32_t *d_ptr = nullptr, *d_idx = nullptr;
-        double *d_val = nullptr;
-        if (hipMalloc((void **)&d_ptr, sizeof(int32_t) * (size_t)(n + 1)) != hipSuccess ||
-            hipMalloc((void **)&d_idx, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)) != hipSuccess ||
-            hipMalloc((void **)&d_val, sizeof(double) * (size_t)std::max<int64_t>(nnz, 1)) != hipSuccess ||
-            hipMemcpy(d_ptr, indptr[k], sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_idx, indices[k], sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_val, data[k], sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice) != hipSuccess) {
+        const size_t nnz = (size_t)indptr[k][n];
+        stk_dev_arrays matrix;
+        const int32_t *d_ptr = matrix.upload(indptr[k], (size_t)n + 1), *d_idx = matrix.upload(indices[k], nnz);
+        const double *d_val = matrix.upload(data[k], nnz);
+        if (!d_ptr || !d_idx || !d_val) {
             stk_set_error("stk_mg_set_member_matrices: device copy of matrix %d failed", k);
             rc = 1;
         } else {
@@ -835,11 +821,9 @@ int stk_coarse_plan_set_members(stk_coarse_plan *p, int level, int n_kinds, int3
                 rc = 1;
             }
         }
-        (void)hipFree(d_ptr), (void)hipFree(d_idx), (void)hipFree(d_val);
     }
     int32_t n_missing = 0;
     if (rc == 0 && hipMemcpy(&n_missing, missing, sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = 1;
-    (void)hipFree(missing);
     if (rc) return rc;
     STK_REQUIRE(n_missing == 0, "stk_mg_set_member_matrices: %d rows of level %d lack their diagonal entry", n_missing,
                 level);
@@ -933,9 +917,8 @@ stk_coarse_plan *stk_coarse_plan_build(const stk_coarse_level *lv, int Lc, int s
     }
     p->n_jobs = (int)J.size();
     p->Lc = Lc;
-    if (hipMalloc((void **)&p->dev_jobs, sizeof(Job) * J.size()) != hipSuccess ||
-        hipMemcpy(p->dev_jobs, J.data(), sizeof(Job) * J.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        stk_coarse_plan_free(p);
+    if (!(p->dev_jobs = p->dev.upload(J))) {
+        delete p;
         return nullptr;
     }
     build_uniform(p);  // optional: the plan works without it

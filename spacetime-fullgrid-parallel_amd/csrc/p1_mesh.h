@@ -5,7 +5,7 @@
 // points of a cell and of the time bracket of a pair, and the host side of a plan -- the
 // opening checks (p1_plan_open: the arguments, the mesh, the vertex -> slab-row map), the int32
 // cells and the device arrays (p1_mesh_upload), |T| and the gradients of every cell
-// (p1_geometry) and what frees a plan's arrays (p1_free).  Everything is file-local: a
+// (p1_geometry), all allocated from the plan's stk_dev_arrays.  Everything is file-local: a
 // translation unit that includes this gets its own copy, its kernels in its own code object.
 //
 // ARITHMETIC: every product and every sum rounded on its own.  Contraction is SWITCHED OFF
@@ -13,7 +13,7 @@
 // with -ffp-contract=off (Makefile), and nothing here calls fma.
 #pragma once
 #include <cmath>
-#include <initializer_list>
+#include <string>
 #include <vector>
 
 #include "stk_common.h"
@@ -246,64 +246,51 @@ inline int p1_hip(const char *who, hipError_t e)
     return e != hipSuccess;
 }
 
-// the device arrays a plan holds, freed where they are set
-inline void p1_free(std::initializer_list<void *> arrays)
+// an allocation of a plan's set-up that came back null: "<who>: <what the owner's seam said>"
+inline int p1_no_array(const char *who)
 {
-    for (void *a : arrays)
-        if (a) (void)hipFree(a);
+    const std::string why = stk_last_error();
+    stk_set_error("%s: %s", who, why.c_str());
+    return 1;
 }
 
-template <typename T>
-int p1_upload(T **dst, const T *src, size_t n)
-{
-    STK_HIP(hipMalloc((void **)dst, (n ? n : 1) * sizeof(T)));
-    if (n) STK_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// the device arrays of a checked mesh; a plan embeds one and frees it with p1_mesh_free
+// the device arrays of a checked mesh; a plan embeds one, its stk_dev_arrays owns them
 struct p1_mesh_dev {
     double *points;   // [nv][d]
     int32_t *cells;   // [nc][d + 1]
     int32_t *row_of;  // [nv], or null where the plan needs none
 };
 
-inline int p1_mesh_upload(p1_mesh_dev *m, int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells,
-                          const std::vector<int32_t> *row_of)
+inline int p1_mesh_upload(stk_dev_arrays &dev, p1_mesh_dev *m, int32_t d, int64_t nv, int64_t nc, const double *points,
+                          const int64_t *cells, const std::vector<int32_t> *row_of)
 {
     std::vector<int32_t> cells32((size_t)(d + 1) * nc);
     for (size_t q = 0; q < cells32.size(); ++q) cells32[q] = (int32_t)cells[q];
-    int rc = p1_upload(&m->points, points, (size_t)nv * d);
-    if (!rc) rc = p1_upload(&m->cells, cells32.data(), cells32.size());
-    if (!rc && row_of) rc = p1_upload(&m->row_of, row_of->data(), row_of->size());
-    return rc;
-}
-
-inline void p1_mesh_free(p1_mesh_dev *m)
-{
-    p1_free({m->points, m->cells, m->row_of});
+    m->points = dev.upload(points, (size_t)nv * d);
+    m->cells = dev.upload(cells32);
+    if (row_of) m->row_of = dev.upload(*row_of);
+    return !m->points || !m->cells || (row_of && !m->row_of);
 }
 
 // plan->grad [nc][d + 1][d] and, where the plan wants |T|, *vol [nc] of the plan's uploaded mesh:
-// allocated here, filled by p1_geometry_kernel on the null stream, complete on return.  A
-// template over the plan, so that only a file that calls it carries the kernel.
+// allocated here from the plan's owner, filled by p1_geometry_kernel on the null stream,
+// complete on return.  A template over the plan, so that only a file that calls it carries
+// the kernel.
 template <class Plan>
-int p1_geometry(const char *who, Plan *plan, double **vol)
+int p1_geometry(const char *who, stk_dev_arrays &dev, Plan *plan, double **vol)
 {
     const int32_t d = plan->d;
     const int64_t nc = plan->nc;
     const p1_mesh_dev &m = plan->mesh;
-    hipError_t e = vol ? hipMalloc((void **)vol, (size_t)nc * sizeof(double)) : hipSuccess;
-    if (e == hipSuccess) e = hipMalloc((void **)&plan->grad, (size_t)(d + 1) * nc * d * sizeof(double));
-    if (e == hipSuccess) {
-        const dim3 grid(stk_flat_grid(nc, P1_BS));
-        double *v = vol ? *vol : nullptr;
-        if (d == 2)
-            hipLaunchKernelGGL(p1_geometry_kernel<2>, grid, dim3(P1_BS), 0, 0, nc, m.points, m.cells, v, plan->grad);
-        else
-            hipLaunchKernelGGL(p1_geometry_kernel<3>, grid, dim3(P1_BS), 0, 0, nc, m.points, m.cells, v, plan->grad);
-        e = hipGetLastError();
-    }
+    if (vol && !(*vol = dev.alloc<double>((size_t)nc))) return p1_no_array(who);
+    if (!(plan->grad = dev.alloc<double>((size_t)(d + 1) * nc * d))) return p1_no_array(who);
+    const dim3 grid(stk_flat_grid(nc, P1_BS));
+    double *v = vol ? *vol : nullptr;
+    if (d == 2)
+        hipLaunchKernelGGL(p1_geometry_kernel<2>, grid, dim3(P1_BS), 0, 0, nc, m.points, m.cells, v, plan->grad);
+    else
+        hipLaunchKernelGGL(p1_geometry_kernel<3>, grid, dim3(P1_BS), 0, 0, nc, m.points, m.cells, v, plan->grad);
+    hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
     return p1_hip(who, e);
 }

@@ -36,7 +36,7 @@ struct stk_kron_plan {
     stk_pack_pattern pairs_x{};
     std::vector<double> pairs_x_vals;  // [units][K][2][n_mats]
     std::map<std::vector<int32_t>, double *> pairs_x_for;
-    std::vector<void *> owned;  // every device allocation
+    stk_dev_arrays dev;  // every device allocation
     int64_t nnz_union = 0;
 };
 
@@ -168,17 +168,6 @@ extern "C" int stk_pack_group_rows(int32_t M, int32_t K, const int32_t *counts, 
 
 namespace {
 
-template <typename T>
-int upload(stk_kron_plan *p, const std::vector<T> &host, T **dev)
-{
-    *dev = nullptr;
-    if (host.empty()) return 0;
-    STK_HIP(hipMalloc((void **)dev, host.size() * sizeof(T)));
-    p->owned.push_back(*dev);
-    STK_HIP(hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
 // Row pairs for matrices whose values do not repeat: partners first brought next to
 // each other (stk_pack_match_order), then grouped like the dictionary form with
 // every entry as its own code (its position in the ELL arrays, 0 = no entry).
@@ -216,9 +205,9 @@ int build_explicit_pairs(stk_kron_plan *p, int32_t M, int K, int n_mats, int col
             for (int m = 0; m < n_mats; ++m) p->pairs_x_vals[s2 * n_mats + m] = ell_val[m][(size_t)ent - 1];
     }
     urows.resize(U * rp);
-    uint32_t *d_slots;
-    int32_t *d_urows;
-    if (upload(p, slots, &d_slots) || upload(p, urows, &d_urows)) return 1;
+    uint32_t *d_slots = p->dev.upload(slots);
+    int32_t *d_urows = p->dev.upload(urows);
+    if (!d_slots || !d_urows) return 1;
     p->pairs_x = stk_pack_pattern{M, K2, col_bits, 1, n_mats, rp, (int32_t)U, d_slots, d_urows, nullptr, nullptr};
     p->explicit_pairs = true;
     return 0;
@@ -236,9 +225,9 @@ const stk_pack_pattern *explicit_pattern_for(stk_kron_plan *p, int32_t n_terms, 
         std::vector<double> sub(slots * n_terms);
         for (size_t s2 = 0; s2 < slots; ++s2)
             for (int k = 0; k < n_terms; ++k) sub[s2 * n_terms + k] = p->pairs_x_vals[s2 * p->n_mats + mats[k]];
-        double *dev = nullptr;
-        if (upload(p, sub, &dev)) return nullptr;
-        it = p->pairs_x_for.emplace(mats, dev).first;
+        double *d_sub = p->dev.upload(sub);
+        if (!d_sub) return nullptr;
+        it = p->pairs_x_for.emplace(mats, d_sub).first;
     }
     *out = p->pairs_x;
     out->n_mats = n_terms;
@@ -303,15 +292,16 @@ int build(stk_kron_plan *p, int32_t M, int32_t n_mats, const int32_t *const *ind
         ovf_ptr[pos + 1] = (int32_t)ovf_idx.size();
     }
     const bool overflow = !ovf_idx.empty();
-    int32_t *d_idx, *d_rows, *d_optr = nullptr, *d_oidx = nullptr;
-    if (upload(p, ell_idx, &d_idx) || upload(p, row_ids, &d_rows)) return 1;
-    if (overflow && (upload(p, ovf_ptr, &d_optr) || upload(p, ovf_idx, &d_oidx))) return 1;
+    int32_t *d_idx = p->dev.upload(ell_idx), *d_rows = p->dev.upload(row_ids);
+    int32_t *d_optr = overflow ? p->dev.upload(ovf_ptr) : nullptr;
+    int32_t *d_oidx = overflow ? p->dev.upload(ovf_idx) : nullptr;
+    if (!d_idx || !d_rows || (overflow && (!d_optr || !d_oidx))) return 1;
     p->ell = stk_ell_pattern{M, K, d_idx, order ? d_rows : nullptr, d_optr, d_oidx};
-    p->ell_vals.resize(n_mats);
+    p->ell_vals.assign(n_mats, nullptr);
     p->ovf_vals.assign(n_mats, nullptr);
     for (int m = 0; m < n_mats; ++m) {
-        if (upload(p, ell_val[m], &p->ell_vals[m])) return 1;
-        if (overflow && upload(p, ovf_val[m], &p->ovf_vals[m])) return 1;
+        if (!(p->ell_vals[m] = p->dev.upload(ell_val[m]))) return 1;
+        if (overflow && !(p->ovf_vals[m] = p->dev.upload(ovf_val[m]))) return 1;
     }
     // ---- dictionary of value tuples, packed slots, row records ------------------
     if (overflow) return 0;
@@ -348,9 +338,9 @@ int build(stk_kron_plan *p, int32_t M, int32_t n_mats, const int32_t *const *ind
         for (int m = 0; m < n_mats; ++m) std::memcpy(&table[(size_t)m * n_codes + rank[kv.second]], &kv.first[m], 8);
     std::vector<uint32_t> slots_w((size_t)M * K);
     for (size_t s = 0; s < (size_t)M * K; ++s) slots_w[s] = (rank[code[s]] << col_bits) | (uint32_t)ell_idx[s];
-    uint32_t *d_slots;
-    double *d_dict;
-    if (upload(p, slots_w, &d_slots) || upload(p, table, &d_dict)) return 1;
+    uint32_t *d_slots = p->dev.upload(slots_w);
+    double *d_dict = p->dev.upload(table);
+    if (!d_slots || !d_dict) return 1;
     p->pack = stk_pack_pattern{M, K, col_bits, n_codes, n_mats, 1, M, d_slots, order ? d_rows : nullptr, d_dict};
     p->packed = true;
     // ---- several rows per slot row (stk_pack_group_rows above; source/linop.py
@@ -402,10 +392,10 @@ int build(stk_kron_plan *p, int32_t M, int32_t n_mats, const int32_t *const *ind
     for (size_t s2 = 0; s2 < U * K2; ++s2)
         pair_slots[s2] = (unit_codes[combined[s2]] << col_bits) | (uint32_t)ucol[s2];
     urows.resize(U * rp);
-    uint32_t *d_pslots;
-    int32_t *d_urows;
-    double *d_pdict;
-    if (upload(p, pair_slots, &d_pslots) || upload(p, urows, &d_urows) || upload(p, pair_table, &d_pdict)) return 1;
+    uint32_t *d_pslots = p->dev.upload(pair_slots);
+    int32_t *d_urows = p->dev.upload(urows);
+    double *d_pdict = p->dev.upload(pair_table);
+    if (!d_pslots || !d_urows || !d_pdict) return 1;
     p->pack_pairs = stk_pack_pattern{M, K2, col_bits, n_pair, n_mats, rp, (int32_t)U, d_pslots, d_urows, d_pdict};
     p->paired = true;
     return 0;
@@ -438,7 +428,7 @@ extern "C" int stk_kron_plan_create(int32_t M, int32_t n_mats, const int32_t *co
     p->pack_rows = stk_tune(g_tuning.pack_rows);
     const int rc = build(p, M, n_mats, indptr_host, indices_host, data_host, row_order_host);
     if (rc) {
-        stk_kron_plan_destroy(p);
+        delete p;
         return rc;
     }
     *out = p;
@@ -447,8 +437,6 @@ extern "C" int stk_kron_plan_create(int32_t M, int32_t n_mats, const int32_t *co
 
 extern "C" int stk_kron_plan_destroy(stk_kron_plan *p)
 {
-    if (!p) return 0;
-    for (void *d : p->owned) (void)hipFree(d);
     delete p;
     return 0;
 }

@@ -511,21 +511,13 @@ struct stk_sample_plan {
     size_t req_bytes;
     hipEvent_t copied;
     bool copy_pending;
+    stk_dev_arrays dev;  // owns every device array above (req_host and the event go by hand)
+    ~stk_sample_plan()
+    {
+        if (req_host) (void)hipHostFree(req_host);
+        if (copied) (void)hipEventDestroy(copied);
+    }
 };
-
-namespace {
-
-void release(stk_sample_plan *p)
-{
-    if (!p) return;
-    p1_mesh_free(&p->mesh);
-    p1_free({p->bin_ptr, p->bin_cells, p->req_dev});
-    if (p->req_host) (void)hipHostFree(p->req_host);
-    if (p->copied) (void)hipEventDestroy(p->copied);
-    delete p;
-}
-
-}  // namespace
 
 extern "C" int stk_sample_grid_build(int32_t d, int64_t nv, int64_t nc, const double *points, const int64_t *cells,
                                      stk_sample_grid **out)
@@ -655,16 +647,15 @@ extern "C" int stk_sample_plan_create(int32_t d, int64_t nv, int64_t nc, const d
     stk_sample_plan *p = new stk_sample_plan();
     p->d = d, p->nv = nv, p->nc = nc, p->n_free = n_free;
     for (int k = 0; k < 3; ++k) p->g.nb[k] = grid->nb[k], p->g.lo[k] = grid->lo[k], p->g.inv_w[k] = grid->inv_w[k];
-    int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, cells, &row_of);
-    if (!rc) rc = p1_upload(&p->bin_ptr, grid->bin_ptr.data(), grid->bin_ptr.size());
-    if (!rc) rc = p1_upload(&p->bin_cells, grid->bin_cells.data(), grid->bin_cells.size());
+    int rc = p1_mesh_upload(p->dev, &p->mesh, d, nv, nc, points, cells, &row_of);
+    if (!rc) rc = !(p->bin_ptr = p->dev.upload(grid->bin_ptr)) || !(p->bin_cells = p->dev.upload(grid->bin_cells));
     stk_sample_grid_free(grid);
     if (!rc && hipEventCreateWithFlags(&p->copied, hipEventDisableTiming) != hipSuccess) {
         stk_set_error("stk_sample_plan_create: no event");
         rc = 1;
     }
     if (rc) {
-        release(p);
+        delete p;
         return rc;
     }
     *out = p;
@@ -673,7 +664,7 @@ extern "C" int stk_sample_plan_create(int32_t d, int64_t nv, int64_t nc, const d
 
 extern "C" int stk_sample_plan_destroy(stk_sample_plan *plan)
 {
-    release(plan);
+    delete plan;
     return 0;
 }
 
@@ -757,11 +748,11 @@ extern "C" int stk_sample_eval(void *stream, stk_sample_plan *plan, int64_t n_p,
     if (bytes > plan->req_bytes) {
         // the device image may still be read by an earlier call's kernels
         STK_HIP(hipStreamSynchronize(st));
-        if (plan->req_dev) (void)hipFree(plan->req_dev);
+        plan->dev.release(plan->req_dev);
         if (plan->req_host) (void)hipHostFree(plan->req_host);
         plan->req_dev = plan->req_host = nullptr, plan->req_bytes = 0;
         const size_t room = std::max<size_t>(2 * bytes, 4096);
-        STK_HIP(hipMalloc((void **)&plan->req_dev, room));
+        if (!(plan->req_dev = plan->dev.alloc<char>(room))) return 1;
         STK_HIP(hipHostMalloc((void **)&plan->req_host, room, hipHostMallocDefault));
         plan->req_bytes = room;
     }

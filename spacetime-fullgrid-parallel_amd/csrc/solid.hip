@@ -50,6 +50,7 @@ struct stk_solid_plan {
     int32_t *tile_ptr;   // [n_tiles + 1]
     int32_t *tile_rows;  // [tile_ptr[n_tiles]]
     uint16_t *cell_pos;  // [nc][d + 1]: the position in the tile's list, SOLID_NO_ROW on the boundary
+    stk_dev_arrays dev;  // owns every device array above
 };
 
 namespace {
@@ -219,14 +220,6 @@ __global__ __launch_bounds__(BS) void solid_scan_kernel(int64_t nc, int32_t n_co
     if (mine) solid_write<D>(s, state, nc, t);
 }
 
-void release(stk_solid_plan *p)
-{
-    if (!p) return;
-    p1_mesh_free(&p->mesh);
-    p1_free({p->grad, p->cell_of, p->tile_ptr, p->tile_rows, p->cell_pos});
-    delete p;
-}
-
 }  // namespace
 
 extern "C" int stk_solid_rows(int32_t d) { return d == 2 || d == 3 ? STK_SOLID_ROWS(d) : 0; }
@@ -343,14 +336,14 @@ extern "C" int stk_solid_plan_create(int32_t d, int64_t nv, int64_t nc, const do
     p->d = d, p->nv = nv, p->nc = nc, p->n_free = n_free, p->n_tiles = n_tiles;
     p->longest = 0;
     for (int64_t i = 0; i < n_tiles; ++i) p->longest = std::max(p->longest, tile_ptr[(size_t)i + 1] - tile_ptr[(size_t)i]);
-    int rc = p1_mesh_upload(&p->mesh, d, nv, nc, points, placed.data(), nullptr);
-    if (!rc) rc = p1_upload(&p->cell_of, order.data(), order.size());
-    if (!rc) rc = p1_upload(&p->tile_ptr, tile_ptr.data(), tile_ptr.size());
-    if (!rc) rc = p1_upload(&p->tile_rows, tile_rows.data(), (size_t)tile_ptr[(size_t)n_tiles]);
-    if (!rc) rc = p1_upload(&p->cell_pos, cell_pos.data(), cell_pos.size());
-    if (!rc) rc = p1_geometry(who, p, nullptr);  // (the scan has no use for |T|)
+    stk_dev_arrays &dev = p->dev;
+    int rc = p1_mesh_upload(dev, &p->mesh, d, nv, nc, points, placed.data(), nullptr);
+    if (!rc) rc = !(p->cell_of = dev.upload(order)) || !(p->tile_ptr = dev.upload(tile_ptr));
+    if (!rc) rc = !(p->tile_rows = dev.upload(tile_rows.data(), (size_t)tile_ptr[(size_t)n_tiles]));
+    if (!rc) rc = !(p->cell_pos = dev.upload(cell_pos));
+    if (!rc) rc = p1_geometry(who, dev, p, nullptr);  // (the scan has no use for |T|)
     if (rc) {
-        release(p);
+        delete p;
         return rc;
     }
     *out = p;
@@ -359,7 +352,7 @@ extern "C" int stk_solid_plan_create(int32_t d, int64_t nv, int64_t nc, const do
 
 extern "C" int stk_solid_plan_destroy(stk_solid_plan *plan)
 {
-    release(plan);
+    delete plan;
     return 0;
 }
 

@@ -107,28 +107,14 @@ __global__ __launch_bounds__(TBS) void sptrsv_kernel(const TriArgs a)
     }
 }
 
-template <class T>
-int upload(const std::vector<T> &h, T **d)
-{
-    STK_HIP(hipMalloc((void **)d, std::max<size_t>(h.size(), 1) * sizeof(T)));
-    if (!h.empty()) STK_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
-void release(TriDev &t)
-{
-    for (void *p : {(void *)t.lvl_ptr, (void *)t.row, (void *)t.ptr, (void *)t.col, (void *)t.val, (void *)t.dinv})
-        (void)hipFree(p);
-    t = TriDev();
-}
-
 // Level-sorted device copy of (a part of) a triangular CSR matrix with sorted column
 // indices: the rows i with take(i), their entries j with keep(j); the dependency depth
 // of a row counts its entries with deps(j) only.  one_level: all rows in one level
 // (none of the kept entries is a dependency among them).  unit: diagonal 1, implicit
-// or explicit.  no_diag: the rows divide by 1 (a product, not a solve).
+// or explicit.  no_diag: the rows divide by 1 (a product, not a solve).  The arrays
+// belong to `dev`, the owner of the plan.
 template <class Take, class Keep, class Deps>
-int build(int32_t n, const int32_t *indptr, const int32_t *indices, const double *data, bool lower, bool unit,
+int build(stk_dev_arrays &dev, int32_t n, const int32_t *indptr, const int32_t *indices, const double *data, bool lower, bool unit,
           Take take, Keep keep, Deps deps, bool one_level, bool no_diag, TriDev *out)
 {
     const char *name = lower ? "L" : "U";
@@ -197,11 +183,9 @@ int build(int32_t n, const int32_t *indptr, const int32_t *indices, const double
         l = b;
     }
     t.depth = depth;
-    if (upload(lvl_ptr, &t.lvl_ptr) || upload(row, &t.row) || upload(ptr, &t.ptr) || upload(col, &t.col) ||
-        upload(val, &t.val) || upload(dinv, &t.dinv)) {
-        release(t);
-        return 1;
-    }
+    t.lvl_ptr = dev.upload(lvl_ptr), t.row = dev.upload(row), t.ptr = dev.upload(ptr);
+    t.col = dev.upload(col), t.val = dev.upload(val), t.dinv = dev.upload(dinv);
+    if (!t.lvl_ptr || !t.row || !t.ptr || !t.col || !t.val || !t.dinv) return 1;
     *out = t;
     return 0;
 }
@@ -294,6 +278,7 @@ struct stk_lu {
     std::vector<int32_t> top_rows_host;
     int32_t *top_rows = nullptr;
     TriDev L_head, L_top, U_head;  // L_top: rows of S, entries outside S (one level, a product)
+    stk_dev_arrays dev;            // every device array of the plan, those of the five TriDev included
     double *L_inv = nullptr, *U_inv = nullptr;  // [n_top][n_top] row-major, set by the caller
     int32_t top_block = 0;                       // rows of a diagonal block (inverted in place)
     double *scratch = nullptr;                   // [top_block][n_loc] between the two launches of a block
@@ -302,11 +287,6 @@ struct stk_lu {
 
 extern "C" int stk_lu_destroy(stk_lu *lu)
 {
-    if (!lu) return 0;
-    release(lu->L), release(lu->U), release(lu->L_head), release(lu->L_top), release(lu->U_head);
-    for (void *p : {(void *)lu->src_perm, (void *)lu->dst_perm, (void *)lu->top_rows, (void *)lu->L_inv,
-                    (void *)lu->U_inv, (void *)lu->scratch})
-        (void)hipFree(p);
     delete lu;
     return 0;
 }
@@ -332,10 +312,11 @@ extern "C" int stk_lu_create(int32_t n, const int32_t *L_indptr, const int32_t *
     stk_lu *lu = new stk_lu;
     lu->n = n;
     auto all = [](int) { return true; };
-    if (build(n, L_indptr, L_indices, L_data, true, true, all, all, all, false, false, &lu->L) ||
-        build(n, U_indptr, U_indices, U_data, false, false, all, all, all, false, false, &lu->U) ||
-        upload(src, &lu->src_perm) || upload(dst, &lu->dst_perm)) {
-        stk_lu_destroy(lu);
+    stk_dev_arrays &dev = lu->dev;
+    if (build(dev, n, L_indptr, L_indices, L_data, true, true, all, all, all, false, false, &lu->L) ||
+        build(dev, n, U_indptr, U_indices, U_data, false, false, all, all, all, false, false, &lu->U) ||
+        !(lu->src_perm = dev.upload(src)) || !(lu->dst_perm = dev.upload(dst))) {
+        delete lu;
         return 1;
     }
     // S: the rows from the first narrow level of L on -- if there are enough levels to
@@ -357,19 +338,16 @@ extern "C" int stk_lu_create(int32_t n, const int32_t *L_indptr, const int32_t *
         if (T.n_levels - d0 >= 16 && n_top >= 2 && n_top <= 40000 && closed) {
             auto top = [&](int i) { return in_top[i] != 0; };
             auto head = [&](int i) { return in_top[i] == 0; };
-            if (build(n, L_indptr, L_indices, L_data, true, true, head, all, all, false, false, &lu->L_head) ||
-                build(n, L_indptr, L_indices, L_data, true, true, top, head, head, true, true, &lu->L_top) ||
-                build(n, U_indptr, U_indices, U_data, false, false, head, all, head, false, false, &lu->U_head)) {
-                stk_lu_destroy(lu);
+            for (int i = 0; i < n; ++i)
+                if (in_top[i]) lu->top_rows_host.push_back(i);
+            if (build(dev, n, L_indptr, L_indices, L_data, true, true, head, all, all, false, false, &lu->L_head) ||
+                build(dev, n, L_indptr, L_indices, L_data, true, true, top, head, head, true, true, &lu->L_top) ||
+                build(dev, n, U_indptr, U_indices, U_data, false, false, head, all, head, false, false, &lu->U_head) ||
+                !(lu->top_rows = dev.upload(lu->top_rows_host))) {
+                delete lu;
                 return 1;
             }
             lu->n_top = n_top;
-            for (int i = 0; i < n; ++i)
-                if (in_top[i]) lu->top_rows_host.push_back(i);
-            if (upload(lu->top_rows_host, &lu->top_rows)) {
-                stk_lu_destroy(lu);
-                return 1;
-            }
         }
     }
     *out = lu;
@@ -391,8 +369,8 @@ extern "C" int stk_lu_set_top_inverse(stk_lu *lu, const double *L_inv_dev, const
     STK_REQUIRE(block >= 1 && block <= 8192, "stk_lu_set_top_inverse: blocks of %d rows (1 .. 8192)", block);
     lu->top_block = block < lu->n_top ? block : lu->n_top;
     const size_t bytes = sizeof(double) * (size_t)lu->n_top * lu->n_top;
-    if (!lu->L_inv) STK_HIP(hipMalloc((void **)&lu->L_inv, bytes));
-    if (!lu->U_inv) STK_HIP(hipMalloc((void **)&lu->U_inv, bytes));
+    if (!lu->L_inv && !(lu->L_inv = lu->dev.alloc<double>(bytes / sizeof(double)))) return 1;
+    if (!lu->U_inv && !(lu->U_inv = lu->dev.alloc<double>(bytes / sizeof(double)))) return 1;
     STK_HIP(hipMemcpy(lu->L_inv, L_inv_dev, bytes, hipMemcpyDeviceToDevice));
     STK_HIP(hipMemcpy(lu->U_inv, U_inv_dev, bytes, hipMemcpyDeviceToDevice));
     return 0;
@@ -431,9 +409,9 @@ extern "C" int stk_lu_solve(stk_lu *lu, void *stream, int32_t n_loc, int32_t ld,
     const int nb = lu->top_block, n_blocks = (lu->n_top + nb - 1) / nb;
     const int64_t need = (int64_t)nb * n_loc;
     if (lu->scratch_doubles < need) {
-        if (lu->scratch) STK_HIP(hipFree(lu->scratch));
-        lu->scratch = nullptr, lu->scratch_doubles = 0;
-        STK_HIP(hipMalloc((void **)&lu->scratch, sizeof(double) * (size_t)need));
+        lu->dev.release(lu->scratch);
+        lu->scratch_doubles = 0;
+        if (!(lu->scratch = lu->dev.alloc<double>((size_t)need))) return 1;
         lu->scratch_doubles = need;
     }
     auto block = [&](int k, int lower, const double *mat, const int32_t *dst, double *out) {

@@ -5,6 +5,7 @@
 #include <atomic>
 #include <cstdint>
 
+#include "dev_arrays.h"
 #include "stk.h"
 
 void stk_set_error(const char *fmt, ...);
@@ -110,8 +111,8 @@ int stk_coarse_plan_set_members(stk_coarse_plan *p, int level, int n_kinds, int3
 int stk_coarse_plan_run(const stk_coarse_plan *p, hipStream_t st, int n_loc, int ld, double ca, const double *cm,
                         const int32_t *kind, const double *coarse_inv);
 
-// The plan takes over device arrays (freed by stk_mg_destroy): mg_build.hip.
-void stk_mg_adopt(stk_mg *mg, void *const *dev_ptrs, int n);
+// The plan's owner of device arrays; mg_build.hip hands over what it built with take().
+stk_dev_arrays &stk_mg_arrays(stk_mg *mg);
 
 // Row-gather engine launcher of rows_ell.hip (mode 0 = SPMM, 1 = Gauss-Seidel group).
 int stk_rows_ell_launch(hipStream_t st, int mode, const stk_ell_rows *e, int32_t pos_begin, int32_t pos_end,

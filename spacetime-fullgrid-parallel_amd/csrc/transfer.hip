@@ -20,6 +20,8 @@
 //
 // ARITHMETIC: every operation rounded on its own -- contraction is SWITCHED OFF for this file
 // (the pragma and -ffp-contract=off in the Makefile), and no kernel here calls fma.
+#include <string>
+
 #include "stk_common.h"
 
 #pragma clang fp contract(off)
@@ -27,6 +29,7 @@
 struct stk_transfer_plan {
     int64_t M_fine, M_coarse;
     int32_t *parents;  // device, [M_fine][2]
+    stk_dev_arrays dev;
 };
 
 namespace {
@@ -185,17 +188,13 @@ extern "C" int stk_transfer_plan_create(int64_t M_fine, int64_t M_coarse, const 
                     "the coarse level: a copy pair without a row to copy",
                     (long long)i, (long long)M_coarse);
     }
-    stk_transfer_plan *plan = new stk_transfer_plan{M_fine, M_coarse, nullptr};
-    if (M_fine > 0) {
-        const size_t bytes = (size_t)M_fine * 2 * sizeof(int32_t);
-        hipError_t e = hipMalloc((void **)&plan->parents, bytes);
-        if (e == hipSuccess) e = hipMemcpy(plan->parents, parents, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            stk_set_error("stk_transfer_plan_create: the upload of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-            if (plan->parents) (void)hipFree(plan->parents);
-            delete plan;
-            return 1;
-        }
+    stk_transfer_plan *plan = new stk_transfer_plan();
+    plan->M_fine = M_fine, plan->M_coarse = M_coarse;
+    if (M_fine > 0 && !(plan->parents = plan->dev.upload(parents, (size_t)M_fine * 2))) {
+        const std::string why = stk_last_error();
+        stk_set_error("stk_transfer_plan_create: the upload of the parents failed: %s", why.c_str());
+        delete plan;
+        return 1;
     }
     *out = plan;
     return 0;
@@ -203,8 +202,6 @@ extern "C" int stk_transfer_plan_create(int64_t M_fine, int64_t M_coarse, const 
 
 extern "C" int stk_transfer_plan_destroy(stk_transfer_plan *plan)
 {
-    if (plan == nullptr) return 0;
-    if (plan->parents) (void)hipFree(plan->parents);
     delete plan;
     return 0;
 }
