@@ -1711,6 +1711,72 @@ int stk_transfer_prolong(void *stream, const stk_transfer_plan *plan, int32_t a,
                          const double *uc, int64_t ldc, int64_t qc_first, int32_t n_cc,
                          double *out, int64_t ld, int64_t k_first, int32_t n_cols);
 
+/* ---- restriction P^T: the adjoint of the level transfer -------------------------------
+ * With P the prolongation above (one space level `parents`, a time levels), the functional
+ * f on the FINE trial space as the functional P^T f on the coarse one: (P^T f) . v = f . (P v).
+ * Residuals, duality-based indicators, and the coarse right-hand side of a functional that
+ * exists only as a fine vector.  Every operation is rounded on its own (no fused
+ * multiply-adds) and every sum has ONE order -- a gather over a transposed table, never an
+ * atomic scatter.
+ *
+ * SPACE.  The entries of the coarse row j, in ascending fine row i: (i, 1.0) where
+ * parents[i] = (j, j); (i, 0.5) where one of the two differing parents is j; a -1 parent
+ * contributes to nobody.  g_j(k) = the left fold of w * f_i(k) over these entries, the first
+ * term starting the sum (no 0.0 + in front); a coarse row without entries gives 0.0.
+ * TIME, a levels in one shot, n_fine nodes with (n_fine - 1) % 2^a == 0.  out_j(q) = the left
+ * fold over k = max(0, ((q - 1) << a) + 1) .. min(n_fine - 1, ((q + 1) << a) - 1), ascending,
+ * of w(k) * g_j(k), the first term starting the sum:
+ *     k == q << a:  w = 1.0
+ *     below it:     w = rem / 2^a,        rem = k - ((q - 1) << a)      (prolong's w1)
+ *     above it:     w = 1.0 - rem / 2^a,  rem = k - (q << a)            (prolong's w0)
+ * For a = 0 out = g; with an identity table g = f: both stages are then exact copies, so
+ * "space with a = 0, then time only" gives the doubles of the fused call.  Several space
+ * levels are chained by the caller: the first call acts on the fine slab and carries all of
+ * a, the later ones use a = 0 on the coarse columns.
+ *
+ * stk_transfer_children (host threads, no GPU, deterministic: a stable counting sort) writes
+ * the transposed table as CSR per coarse row: ptr [M_coarse + 1] and ptr[M_coarse] entries,
+ * at most 2 M_fine -- the caller provides that many --, an entry being
+ *     (fine row << 1) | h,     h = 1 where the weight is 0.5, 0 where it is 1.0,
+ * a non-negative int32; hence M_fine <= STK_RESTRICT_MAX_M_FINE = 2^30, anything above is
+ * refused.  It makes the index checks of stk_transfer_plan_create (one routine serves both).
+ * stk_restrict_plan_create builds that table and uploads it to the current device; the
+ * kernel then reads no row outside [0, M_fine), whatever it is given.
+ *
+ * stk_transfer_restrict computes the coarse columns [q_first, q_first + n_qc) into
+ * out[j*ldc + (q - q_first)] from the fine window [k_first, k_first + n_cols) at
+ * f[i*ld + (k - k_first)]; columns >= n_qc of out are never written; 8-byte alignment
+ * suffices; 64-bit offsets, no atomics, nothing allocated, nothing synchronises.
+ * stk_transfer_restrict_time is the time stage alone over M rows (g = f); it needs no
+ * table.  Both refuse (non-zero, stk_last_error names the argument, out untouched): a null
+ * plan, f or out, a outside [0, STK_TRANSFER_MAX_A], negative sizes or node numbers,
+ * ld < n_cols, ldc < n_qc, (n_fine - 1) % 2^a != 0, a q beyond (n_fine - 1) >> a, and a fine
+ * window that does not cover every column the stencils read after clipping to
+ * [0, n_fine - 1].  n_qc == 0 or M_coarse == 0 is a no-op; M_fine == 0 with M_coarse > 0
+ * writes 0.0.
+ *
+ * stk_restrict_tile sets the launch form for the calls that follow, process-wide
+ * (measurement and tests; results never depend on it): `rows` of the coarse level per
+ * workgroup, 1..256, and the LDS a workgroup may take in KiB, 1..64; 0 for either = the
+ * default.  Columns are cut into chunks of whole stencils that fit; where `rows` stencils
+ * do not fit, fewer rows are taken, and one row of one stencil (at most 4 088 bytes) is
+ * always allowed.  Anything else is refused and changes nothing. */
+#define STK_RESTRICT_MAX_M_FINE 1073741824
+typedef struct stk_restrict_plan stk_restrict_plan;
+int stk_transfer_children(int64_t M_fine, int64_t M_coarse, const int32_t *parents,
+                          int64_t *ptr, int32_t *entries);
+int stk_restrict_plan_create(int64_t M_fine, int64_t M_coarse, const int32_t *parents,
+                             stk_restrict_plan **out);
+int stk_restrict_plan_destroy(stk_restrict_plan *plan);
+int stk_restrict_tile(int32_t rows, int32_t lds_kib);
+int stk_transfer_restrict(void *stream, const stk_restrict_plan *plan, int32_t a,
+                          const double *f, int64_t ld, int64_t k_first, int32_t n_cols,
+                          int64_t n_fine, double *out, int64_t ldc, int64_t q_first,
+                          int32_t n_qc);
+int stk_transfer_restrict_time(void *stream, int64_t M, int32_t a, const double *f,
+                               int64_t ld, int64_t k_first, int32_t n_cols, int64_t n_fine,
+                               double *out, int64_t ldc, int64_t q_first, int32_t n_qc);
+
 /* ---- plan construction on the host threads: processing order and union pattern ---
  * stk_tile_order: the mesh-tile order of n dofs with coordinates coords [n][d]
  * (d = 2 or 3): the bounding box cut into cubes of edge `side` from the corner `lo`

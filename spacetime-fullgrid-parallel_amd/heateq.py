@@ -222,7 +222,7 @@ def main(argv=None):
     if levels:
         u, iters, _ = driver.solve_nested(
             heat, lambda J_time, J_space: HeatEquation(**dict(vars(args), J_time=J_time, J_space=J_space)), levels,
-            callback=progress)
+            rhs=heat.f if asked['nested'].nested_rhs == 'restricted' else None, callback=progress)
     else:
         u, iters = heat.solve(callback=progress)
     print('Done in %d  PCG steps. X-norm algebraic error: %s. Error in Yprime: %s\n'

@@ -601,7 +601,8 @@ def main(argv=None):
         solution, iters, per_level = driver.solve_nested(
             heat, lambda J_time, J_space: HeatEquationMPI(**dict(driver.solver_arguments(args), J_time=J_time,
                                                                  J_space=J_space)),
-            levels, rank, callback=progress, history=history)
+            levels, rank, rhs=heat.f if asked['nested'].nested_rhs == 'restricted' else None, callback=progress,
+            history=history)
         record.update(nested=per_level)
     elif heat.f is None:
         solution, iters = PCG(heat.WT_S_W, heat.P, heat.rhs, callback=progress,

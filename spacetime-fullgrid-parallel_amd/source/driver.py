@@ -70,6 +70,8 @@ ISO_OPTIONS = (
 NESTED_OPTIONS = (
     ('nested', int, 0, 'solve the L coarser problems (J_time - l, J_space - l), l = L .. 1, first, from the coarsest up,'
      ' each started from the prolonged solution of the one before (prolong_from, solve(x0=)); default 0: none'),
+    ('nested_rhs', str, 'own', 'right-hand side of the coarser problems of --nested: own (each level assembles its f'
+     ' from the forcing; the default) or restricted (P^T f of the finest level\'s f, restrict_to)'),
 )
 
 
@@ -190,6 +192,8 @@ def take_post_options(args):
         raise SystemExit('--iso_every must be at least 1')
     if asked['nested'] is not None and asked['nested'].nested < 0:
         raise SystemExit('--nested must be at least 0')
+    if asked['nested'] is not None and asked['nested'].nested_rhs not in ('own', 'restricted'):
+        raise SystemExit('--nested_rhs must be own or restricted, not %r' % asked['nested'].nested_rhs)
     return args, asked
 
 
@@ -207,25 +211,36 @@ def nested_levels(J_time, J_space, nested, size=1):
     return levels
 
 
-def solve_nested(heat, build, levels, rank=0, **solve_arguments):
+def solve_nested(heat, build, levels, rank=0, rhs=None, **solve_arguments):
     """Nested iteration: ``build(J_time, J_space)`` makes the driver object of each of `levels`
     (nested_levels: the coarsest first); every level is solved from the prolonged solution of
     the one before it (heat.prolong_from, solve(x0=)), the coarsest from zero, `heat` last.
-    Rank 0 prints one line with the iterations per level.  `solve_arguments` (callback,
-    history, ...) go to the LAST solve.  Returns (u, iterations) of `heat`, and the list of
-    (J_time, J_space, iterations) of all levels; collective."""
-    if heat.f is None:  # before a coarser problem is built
+    `rhs`: a functional on `heat`'s trial space (what ``sample_along_adjoint`` returned, heat.f
+    itself) in place of every level's own f -- a coarser level solves for
+    ``heat.restrict_to(level, rhs)``, `heat` for ``solve(rhs=rhs, x0=...)``.  Rank 0 prints one
+    line with the iterations per level, and with `rhs` which right-hand side the level used.
+    `solve_arguments` (callback, history, ...) go to the LAST solve.  Returns (u, iterations) of
+    `heat`, and the list of (J_time, J_space, iterations) of all levels; collective."""
+    if rhs is None and heat.f is None:  # before a coarser problem is built
         raise SystemExit('--nested: solve() is the path of a problem with forcing; this problem has none')
     before, u, counts = None, None, []
     for number, level in enumerate(list(levels) + [None]):
         this = heat if level is None else build(*level)
         x0 = None if before is None else this.prolong_from(before, u)
-        u, iters = this.solve(x0=x0, **(solve_arguments if level is None else {}))
+        if rhs is None:
+            u, iters = this.solve(x0=x0, **(solve_arguments if level is None else {}))
+            said = ''
+        elif level is None:
+            u, iters = this.solve(rhs=rhs, x0=x0, **solve_arguments)
+            said = ', for the given right-hand side'
+        else:
+            u, iters = this.solve(rhs=heat.restrict_to(this, rhs), x0=x0)
+            said = ', for the restricted right-hand side'
         mesh_space, mesh_time = this._sample_meshes
         counts.append((int(mesh_time.N_el).bit_length() - 1, mesh_space.J - 1, iters))
         if rank == 0:
-            print('\nNested level %d of %d (J_time = %d, J_space = %d): %d PCG steps%s.'
-                  % ((number, len(levels)) + counts[-1] + ('' if x0 is not None else ', from zero',)))
+            print('\nNested level %d of %d (J_time = %d, J_space = %d): %d PCG steps%s%s.'
+                  % ((number, len(levels)) + counts[-1] + ('' if x0 is not None else ', from zero', said)))
         before = this
     return u, iters, counts
 

@@ -1,7 +1,7 @@
 """What both solve drivers (heateq.py, heateq_mpi.py) offer on a solution once it is there:
 sampling, its adjoint, the history maps, the time curves, the solidification maps, the
-isotherms, the error norms and the prolongation of a coarser level's vector -- the ten public
-methods, once, with the plans they build on first use.
+isotherms, the error norms, the prolongation of a coarser level's vector and the restriction
+of a functional to a coarser level -- the eleven public methods, once, with the plans they build on first use.
 
 A driver inherits ``PostProcessing``, calls ``_init_postprocessing`` from its constructor and
 supplies what truly differs as two hooks: how `u` becomes a trial-space device vector
@@ -21,7 +21,7 @@ class PostProcessing:
         self._sample_meshes = (mesh_space, mesh_time)
         self._exact = (data.get('exact'), data.get('exact_grad'))
         self.sample_plan = self.error_plan = self.curves_plan = self.solid_plan = None
-        self.transfer_plans = {}  # per coarse discretisation, built by the first prolong_from() of it
+        self.transfer_plans = {}  # per coarse discretisation, built by the first prolong_from() or restrict_to() of it
 
     # ---- what a driver supplies -----------------------------------------------------------------
     def _trial_vector(self, u, who):
@@ -52,7 +52,7 @@ class PostProcessing:
         self._trial_vector(u, 'sampling')
         return self._sample_plan()
 
-    # ---- the ten methods ------------------------------------------------------------------------
+    # ---- the eleven methods ---------------------------------------------------------------------
     def sample(self, u, times, points, field='u'):
         """u_h(t_k, x_p) of a trial-space vector `u` (KronVectorMPI: a solution, an iterate)
         at `times` (n_k,) in [0, T] and `points` (n_p, d) -- NumPy array, device tensor, or
@@ -262,10 +262,32 @@ class PostProcessing:
         prefix of the fine ones, T the same, the time elements in a ratio 2^a, a <= 8 -- raise
         ValueError before anything touches the GPU.  The plan is cached per coarse
         discretisation (``transfer_plans``) and built by the first call; a run that never asks
-        builds nothing.  Out of scope: the adjoint P^T, injection and restriction, test-space
+        builds nothing.  The adjoint is ``restrict_to``.  Out of scope: injection, test-space
         vectors, a neighbour-only exchange of the coarse columns, other time ratios, different
         coarsest meshes.  The serial driver also takes `u_coarse` as a flat NumPy vector or a
         device vector and returns a device vector (source.linop.host_vector copies it out;
         ``solve(x0=...)`` takes it as it is)."""
         from .transfer import prolong_from
         return prolong_from(self, coarse_heat, u_coarse)
+
+    def restrict_to(self, coarse_heat, f):
+        """P^T f: the FUNCTIONAL `f` on this discretisation's trial space (a right-hand side, a
+        residual f - S u, what ``sample_along_adjoint`` returned) as the functional on the trial
+        space of the COARSER discretisation `coarse_heat` with (P^T f) . v = f . (P v) for P of
+        ``coarse_heat -> self`` (``prolong_from``) -- from one gather pass on the device
+        (source/transfer.py, csrc/transfer.hip): a coarse row folds its own fine row (weight 1.0)
+        and its children (0.5) in ascending fine row, then the 2^(a+1) - 1 fine nodes around its
+        time node in ascending order with prolong's weights, every operation rounded on its own,
+        no atomics.  Returns a new KronVectorMPI on `coarse_heat`'s distribution: the right-hand
+        side of the coarse levels of a nested solve for a functional (``solve_nested(rhs=)``), and
+        E_c^T = P^T E_f^T for point data.  COLLECTIVE and independent of the number of ranks, bit
+        for bit: the last space level acts on every rank's own columns, one all-reduce with one
+        non-zero contributor per entry, then the time stage and the remaining levels on the
+        coarse columns a rank owns.  The checks and the plan cache are those of ``prolong_from``
+        (``transfer_plans``); meshes that are not nested raise ValueError before anything touches
+        the GPU; the transposed tables are built by the first restriction, a run that never
+        restricts builds nothing of them.  Out of scope: injection, test-space vectors, a
+        neighbour-only exchange, other time ratios.  The serial driver also takes `f` as a flat
+        NumPy vector or a device vector."""
+        from .transfer import restrict_to
+        return restrict_to(self, coarse_heat, f)
