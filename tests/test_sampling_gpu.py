@@ -99,7 +99,7 @@ def _times(N, n_k):
     return pool[:n_k]
 
 
-@pytest.mark.parametrize('N', [5, 9, 65])
+@pytest.mark.parametrize('N', [5, 9, 65, 129, 200])
 @pytest.mark.parametrize('problem,J', MESHES)
 def test_evaluate(problem, J, N):
     mesh, plan = mesh_of(problem, J), plan_of(problem, J)
@@ -111,7 +111,7 @@ def test_evaluate(problem, J, N):
     vec, U = _slab(plan.n_free, N, seed=N + J)
     tol = VALUE_TOL * np.max(np.abs(U))
     worst = 0.0
-    for n_k in (1, 2, 7, 65, 130):
+    for n_k in (1, 2, 7, 65, 130, 2 * N + 1):  # the last: 0, T, every node and every midpoint
         times = _times(N, n_k)
         got = plan.evaluate(vec, times, loc).cpu().numpy()
         want = numpy_sample(mesh, U, times, points, located=located_o)
