@@ -12,6 +12,7 @@ import scipy.sparse.linalg as spla
 import torch
 
 from conftest import relerr
+from test_quadrature_reference_host import _longdouble_load
 from test_spacetime_load_host import numpy_load, sum_of_pairs
 
 pytestmark = pytest.mark.gpu
@@ -131,27 +132,6 @@ def test_columns_kernel_equals_the_host_sums(problem, J_space):
                             buf = torch.from_numpy(old).cuda()
                             plan.columns(f_dev, coef, buf, e, accumulate=accumulate, qw=qw, ql=ql)
                             assert np.array_equal(buf.cpu().numpy(), expect), (problem, nq, n_k, n_el, e, accumulate, name)
-
-
-def _longdouble_load(mesh, qw, ql, f, coef):
-    """(want, magnitude, incident cells) of the pair sum_k coef[k][a] L_k in np.longdouble
-    and the same sums over absolute values."""
-    from source.assembly import _simplex_volumes, free_dofs
-    ld = np.longdouble
-    c, fd = mesh.cells, free_dofs(mesh)
-    vol = _simplex_volumes(mesh).astype(ld)
-
-    def run(f, qw, ql, coef):
-        out = np.zeros((len(fd), 2), dtype=ld)
-        for k in range(f.shape[0]):
-            loc = np.matmul(f[k].astype(ld) * qw.astype(ld), ql.astype(ld)) * vol[:, None]
-            vec = np.zeros(mesh.nv, dtype=ld)
-            np.add.at(vec, c.reshape(-1), loc.reshape(-1))
-            out += coef[k].astype(ld)[None, :] * vec[fd][:, None]
-        return out
-
-    incident = np.bincount(c.reshape(-1), minlength=mesh.nv)[fd]
-    return run(f, qw, ql, coef), np.asarray(run(np.abs(f), np.abs(qw), np.abs(ql), np.abs(coef)), dtype=np.float64), incident
 
 
 @pytest.mark.parametrize('J_space', [1, 2])

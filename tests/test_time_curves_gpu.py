@@ -7,6 +7,7 @@ import functools
 import importlib.util
 import os
 import threading
+import types
 
 import numpy as np
 import pytest
@@ -147,6 +148,69 @@ def test_nan_and_inf_in_the_slab_give_what_the_contract_gives(name):
     for theta in (0.3, -INF):
         got = _eval(case, _slab(U), 5, theta)
         assert same(got, case.contract(U, theta)), (name, theta)
+
+
+def _faces_by_sorting(cells):
+    """numpy_boundary_faces without its loop over the cells: the face keys of all cells sorted and
+    counted at once."""
+    nc, nl = cells.shape
+    keys = np.concatenate([np.sort(np.delete(cells, a, axis=1), axis=1) for a in range(nl)])
+    _, inverse, count = np.unique(keys, axis=0, return_inverse=True, return_counts=True)
+    alone = (count[inverse.reshape(-1)] == 1).reshape(nl, nc)
+    mask = np.zeros(nc, dtype=np.uint8)
+    for a in range(nl):
+        mask |= alone[a].astype(np.uint8) << a
+    return mask
+
+
+# more than 256 tiles: the finish kernel adds in place in global memory before it goes to LDS
+PAST_256_TILES = {
+    # 258 cell tiles (one step, two partners) beside 1021 row tiles for the peak and the box (two steps)
+    'square8 first 65793': lambda: first_cells(_mesh('square', 8), 65793),
+    # 512 cell tiles: one step with every partner present
+    'square7': lambda: _mesh('square', 7),
+    # 2048 cell tiles: three steps, every partner present
+    'square8': lambda: _mesh('square', 8),
+    # 3 cell tiles beside 4088 row tiles: the sums stay in LDS, the peak and the box take four steps
+    'square9 first 513': lambda: first_cells(_mesh('square', 9), 513),
+}
+
+
+@pytest.mark.parametrize('name', sorted(PAST_256_TILES))
+def test_finish_kernel_past_256_tiles(name):
+    """The global stage of curves_finish_kernel, with its four kinds of join and n_tiles differing
+    from n_work, against the contract: 1 and 3 columns, theta = 0.3 and +inf.  A peak planted in
+    tile 0 and again, with the same value, in a tile at or above 256 comes back with the lower
+    row -- the tie rule of the join across a global step; in the third column the two equal peaks
+    lie in the tiles 10 and 300.
+    The contract's Python loop over the cells for the boundary faces would take minutes on the
+    whole of square 8; the faces are counted by sorting instead (_faces_by_sorting, checked
+    against that loop on the first 513 cells of every case)."""
+    from source.time_curves import CurvesPlan
+    mesh = PAST_256_TILES[name]()
+    plan = CurvesPlan(mesh, None)
+    points, cells = np.asarray(mesh.points, dtype=np.float64), np.asarray(mesh.cells, dtype=np.int64)
+    case = types.SimpleNamespace(plan=plan, d=plan.d, M=plan.n_free)
+    M, at = case.M, _rows(plan.d)
+    n_tiles, row_tiles = -(-len(cells) // 256), -(-M // 256)
+    assert max(n_tiles, row_tiles) > 256
+    faces = _faces_by_sorting(cells)
+    assert np.array_equal(_faces_by_sorting(cells[:513]), numpy_boundary_faces(cells[:513]))
+    row_of = row_map(mesh)
+    again_0, again_2 = min(256 * 299 + 7, M - 2), min(256 * 300 + 1, M - 1)  # (square 7 has 255 row tiles)
+    for theta in (0.3, INF):
+        U = planted_values(np.random.RandomState(len(cells)), M, 3, 0.3)
+        U[5, 0] = U[again_0, 0] = 9.5
+        U[256 * 10 + 3, 2] = U[again_2, 2] = 9.5
+        want = numpy_time_curves(points, cells, row_of, U, theta, faces=faces)
+        assert want[at['peak_row'], 0] == 5.0 and want[at['peak_row'], 2] == 256.0 * 10 + 3
+        assert want[at['peak'], 0] == 9.5 and want[at['peak'], 2] == 9.5
+        for n in (1, 3):
+            got = _eval(case, _slab(U[:, :n]), n, theta)
+            for q in range(len(want)):
+                assert same(got[q], want[q, :n]), (name, theta, n, q, got[q], want[q, :n])
+            assert not np.isnan(got[:at['peak_row'] + 1]).any()  # no padding column came in
+            assert got[at['peak_row'], 0] == 5.0
 
 
 # ---- 2. every launch form gives the same doubles ---------------------------------------------------------------
